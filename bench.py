@@ -11,7 +11,12 @@ scaling).  `--workload infer` times the 9-generator inference DAG of configs[1] 
 `--workload wsi` the tile-parallel whole-slide loop of configs[4] (synthetic uint8 region in HBM -> crop / is_empty / 9 generators
 on batches of 8 tiles / uint8 stitch; one "step" = one batch of 8 tiles per GPU, every rank owns a band of tile rows).
 Without torchrun, `--gpus N` (N > 1) re-executes itself under `python -m torch.distributed.run --nproc-per-node N`.
-Prints ONE JSON line on rank 0 (contract in the task statement) including
+Prints ONE JSON line on rank 0 (contract in the task statement).  A plain run sets up, warms up, times --steps steps, writes the
+outputs of the last timed step if --dump-outputs DIR is given, and prints the line: `value`, `ms_per_step` and the other headline keys.
+`--dump-outputs DIR` writes what the timed path computed in its last step as DIR/<name>.npy (float32, float64 for scalars): the losses,
+the generated images and a sample of every network's parameters after the update (train workloads), the result images (infer / wsi);
+an output larger than DUMP_SAMPLE elements is kept as a fixed, seeded sample of its elements (the same positions in every run).
+`--full` adds everything else the benchmark measures:
   strict_parity: the SAME workload timed on the strict policy (fp32 storage, split-bf16 x3 MFMA: the one the GPU tests assert at 1e-3
                  against the oracle) plus the measured distance of the headline (bf16) policy from it on this very batch
   roofline     : dominant layer shape = the 3x3, 256->256 ch conv at 8x128x128 pixels (the 18 ResnetBlock convs of every Resnet-9
@@ -22,6 +27,8 @@ Prints ONE JSON line on rank 0 (contract in the task statement) including
                  PMC summary was collected on that same kernel
   cpu_baseline : the CPU oracle (oracle/deepliif_oracle.py, a port of the reference's PyTorch step) timed on this box's host
                  cores for a bounded sample of whole steps at batch 1 (10-30 s of CPU work; rank 0, N=1 only).
+  and graph_replay, exchange, policy_vs_strict, whole_slide, other_workloads (below).  With --full the timed steps carry the roofline's
+  per-launch events, as `value` / `ms_per_step` of the --full line say.
 """
 import argparse
 import json
@@ -44,6 +51,48 @@ STRICT_PMC_FILE = os.path.join('r03', 'pmc_strict_conv256.json')     # the same 
 N8_FULL_FILE = os.path.join('r06', 'cpu_baseline_n8_full.json')     # bench.py --cpu-baseline-n8-full: the oracle at batch 8, 512 x 512 (SURVEY 8d on-spec)
 TRAJECTORY_FILE = os.path.join('r06', 'trajectory_r06.json')  # tests/test_gpu_trajectory.py: 100-step loss curves of both policies vs the oracle
 PMC_FILE = os.path.join('r06', 'pmc_dominant_conv256.json')     # dominant-kernel HBM traffic from separate --pmc passes (re-collected when the kernel changes)
+DUMP_SAMPLE = 1 << 19           # --dump-outputs: elements kept of a larger output (2 MB in float32), at fixed seeded positions
+DUMP_PARAM_SAMPLE = 1 << 16     # --dump-outputs: elements kept of each network's flattened parameters after the step
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def _dump_sample(t, k):
+    """t flattened to float32: all of it up to k elements, else k elements at positions drawn from a fixed seed (same shape -> same positions)"""
+    flat = t.detach().reshape(-1).float()
+    if flat.numel() > k:
+        idx = torch.randint(flat.numel(), (k,), generator=torch.Generator().manual_seed(20240611)).sort().values
+        flat = flat[idx.to(flat.device)]
+    return flat.cpu().numpy()
+
+
+def step_outputs(model, result):
+    """what a caller of the timed path holds after its last step -> {name: ndarray}: the losses (float64), the generated images and a sample of every
+    network's parameters (train workloads, `model`), or the result images (infer: {key: tensor}, wsi: (band images {key: uint8 tensor}, rows))"""
+    import numpy as np
+    out = {}
+    if model is not None:
+        for k, v in model.get_current_losses().items():
+            out[f'loss_{k}'] = np.array(v, dtype=np.float64)
+        for k, v in model.get_current_visuals().items():
+            if k.startswith('fake'):
+                out[k] = _dump_sample(v, DUMP_SAMPLE)
+        for name in model.model_names:
+            params = [p.detach().reshape(-1).float() for p in getattr(model, 'net' + name).parameters()]
+            out[f'param_{name}'] = _dump_sample(torch.cat(params), DUMP_PARAM_SAMPLE)
+    elif isinstance(result, tuple):
+        out.update({k: _dump_sample(v, DUMP_SAMPLE) for k, v in (result[0] or {}).items()})
+    elif result is not None:
+        out.update({k: _dump_sample(v, DUMP_SAMPLE) for k, v in result.items()})
+    return out
+
+
+def dump_outputs(path, arrays):
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_LIMIT_BYTES, f'--dump-outputs: {total} bytes of outputs, more than {DUMP_LIMIT_BYTES}'
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(path, f'{k}.npy'), a)
 
 
 def make_opt(args, device_index, M=5, seg_gen=False):
@@ -239,7 +288,7 @@ def other_workloads(args):
     import subprocess
     out = {}
     for wl in ('infer', 'infer_fp16', 'train18', 'ext', 'wsi', 'wsi_fp16'):
-        cmd = [sys.executable, os.path.abspath(__file__), '--workload', wl.split('_')[0], '--precision', 'fp16' if wl.endswith('_fp16') else args.precision, '--steps', '5', '--warmup', '2', '--no-strict', '--no-graph', '--no-timer-check', '--no-other-workloads',
+        cmd = [sys.executable, os.path.abspath(__file__), '--workload', wl.split('_')[0], '--precision', 'fp16' if wl.endswith('_fp16') else args.precision, '--steps', '5', '--warmup', '2', '--full', '--no-strict', '--no-graph', '--no-timer-check', '--no-other-workloads',
                '--batch', str(args.batch), '--size', str(args.size), '--ngf', str(args.ngf)]
         if wl != 'infer':
             cmd.append('--no-cpu-baseline')
@@ -310,6 +359,11 @@ def main():
                          '2 Resnet-9 + 2 UNet-512 (9-channel input) generators, 2 + 2 discriminators (6 / 12 channels); infer = configs[1]; '
                          'wsi = configs[4], tile-parallel whole-slide inference (synthetic uint8 region, 512 tiles, overlap 32)')
     ap.add_argument('--region', type=int, default=20000, help='wsi workload: side of the synthetic square region in pixels')
+    ap.add_argument('--full', action='store_true', help='after the headline, everything else the benchmark measures: per-launch roofline events in the timed steps '
+                    '(+ the one-stream and no-events passes, the MFMA probe), the strict-parity leg, hipGraph replay, the exchange profile, policy_vs_strict, '
+                    'the whole-slide pass, the CPU baselines and other_workloads; the --no-* options below switch single legs off')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None, help='write what the timed path computed in its last step to DIR/<name>.npy '
+                    f'(float32 / float64; outputs larger than {DUMP_SAMPLE} elements as a fixed, seeded sample; at most {DUMP_LIMIT_BYTES >> 20} MB)')
     ap.add_argument('--no-timer-check', action='store_true', help='skip the second pass that times the same steps WITHOUT the per-launch events '
                     '(roofline.timer_overhead)')
     ap.add_argument('--no-strict', action='store_true', help='skip the strict-parity (fp32 policy) leg')
@@ -437,7 +491,7 @@ def main():
         if args.workload == 'infer':
             tiles = synth(1234)
             infer_state.update(nets=nets, tiles=tiles, opt=iopt, sw=sw)
-            return (lambda: I.run_generators(tiles, nets, iopt, seg_weights=sw)), None, GF_PER_TILE_INFER, dom, \
+            return (lambda: infer_state.update(out=I.run_generators(tiles, nets, iopt, seg_weights=sw))), None, GF_PER_TILE_INFER, dom, \
                 'DeepLIIF inference, 4x Resnet-9block + 5x UNet-512 generators + weighted seg sum (BASELINE configs[1])'
         # wsi: one synthetic region, identical on every rank (seeded noise, so no tile is_empty); rank r infers its band of tile rows
         R = args.region
@@ -480,7 +534,7 @@ def main():
 
     # ---- strict-parity leg, part 1 (before any optimizer step): distance of the headline policy from the strict policy on this batch
     strict = None
-    want_strict = (not args.no_strict) and args.precision != 'fp32' and args.workload in ('train', 'train18', 'ext') and (world == 1 or args.strict)
+    want_strict = args.full and (not args.no_strict) and args.precision != 'fp32' and args.workload in ('train', 'train18', 'ext') and (world == 1 or args.strict)
     if want_strict:
         sstep, smodel, _, _, _ = build('fp32')
         for mdl in (model, smodel):
@@ -506,7 +560,7 @@ def main():
         per_rank = min((r1 - r0) * len(plan.xs) for r0, r1 in rows)           # every rank processes the same number of tiles in the timed region
         n_batches = min(args.steps, per_rank // n)
         assert n_batches >= 1, 'region too small for this many ranks'
-        timer = KernelTimer(backend_of(args.precision), dom_shape) if not dry else types.SimpleNamespace(mean_seconds=lambda: None, pairs=[], kernel='?', enabled=False)
+        timer = KernelTimer(backend_of(args.precision), dom_shape) if args.full and not dry else types.SimpleNamespace(mean_seconds=lambda: None, pairs=[], kernel='?', enabled=False)
         step(n * max(args.warmup, 1))
         barrier()
         timer.enabled = True
@@ -520,7 +574,9 @@ def main():
             torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
             dt = float(t.item())
         args.steps = n_batches
-        if not args.no_wsi_whole:
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, step_outputs(None, wsi_state['bands']))
+        if args.full and not args.no_wsi_whole:
             # configs[4] end to end, once: EVERY tile of this rank's band (crop, is_empty, 9 generators, uint8 paste), then the bands of all ranks gathered on rank 0
             # (inference.gather_bands) -- the stitched result images exist on rank 0 when the clock stops
             from deepliif_amd import inference as I2
@@ -547,11 +603,13 @@ def main():
             del full, local
             wsi_state['bands'] = None
     else:
-        timer = KernelTimer(backend_of(args.precision), dom_shape) if not dry else types.SimpleNamespace(mean_seconds=lambda: None, pairs=[], kernel='?', enabled=False)
-        exch = getattr(model, 'exchange', None) if (model is not None and D.active()) else None
+        timer = KernelTimer(backend_of(args.precision), dom_shape) if args.full and not dry else types.SimpleNamespace(mean_seconds=lambda: None, pairs=[], kernel='?', enabled=False)
+        exch = getattr(model, 'exchange', None) if (args.full and model is not None and D.active()) else None
         if exch is not None:
             exch.profile = not dry          # device-side events around the waits of GradExchanger.finish(): the exposed part of the exchange
         dt = timed(step, args.warmup, args.steps, timer)
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, step_outputs(model, infer_state.get('out')))
         if exch is not None:
             exch.profile = False
             sync()
@@ -672,7 +730,7 @@ def main():
     # ---- hipGraph leg: the same steps replayed from ONE captured graph (models.StepGraph): what the step costs when Python is out of it.  The headline
     # `value` above is the EAGER step (it carries the per-launch events the roofline block needs); this leg runs LAST, on the same model.
     graph_report = None
-    if not args.no_graph and not dry and model is not None and world == 1 and args.workload in ('train', 'train18', 'ext') and args.precision in last_batch:
+    if args.full and not args.no_graph and not dry and model is not None and world == 1 and args.workload in ('train', 'train18', 'ext') and args.precision in last_batch:
         try:
             sg = M.StepGraph(model, warmup=2)
         except Exception as exc:
@@ -778,7 +836,7 @@ def main():
         out['dtype_note'] = ('headline dtype bf16 is the throughput policy (BASELINE.json quotes the target on bf16 MFMA); it does NOT meet the 1e-3 parity bar -- '
                              'its measured distance from the strict policy is in strict_parity.headline_vs_strict; the strict policy (asserted at 1e-3 against '
                              'the oracle by the GPU tests) is timed on the same workload in strict_parity.value')
-    if args.workload == 'infer' and infer_state and not dry and rank == 0 and args.precision != 'fp32':
+    if args.full and args.workload == 'infer' and infer_state and not dry and rank == 0 and args.precision != 'fp32':
         # how far this policy's output images are from the strict policy's (the one the GPU tests hold at 1e-3 against the oracle), same weights, same tiles:
         # max |difference| relative to the strict output's range, per result key, and the share of 8-bit channel values (tensor2im) that differ by more than one level
         from deepliif_amd import inference as I_
@@ -800,9 +858,9 @@ def main():
         out['data'] = 'DRY RUN on CPU through the test emulation backend (launch-path check only; numbers are meaningless)'
     if whole_slide is not None:
         out['whole_slide'] = whole_slide
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and args.workload == 'infer' and not dry:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and args.workload == 'infer' and not dry:
         out['cpu_baseline'] = cpu_baseline_infer(args)
-    elif rank == 0 and world == 1 and not args.no_cpu_baseline and args.workload == 'train' and not dry:
+    elif args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and args.workload == 'train' and not dry:
         out['cpu_baseline'] = cpu_baseline(args)
         if not args.no_cpu_baseline_n8 and args.batch != args.cpu_batch:
             # "N=1 (reference default batch_size) and N=8": the same oracle at the GPU line's per-GPU batch.  A batch-8 step at
@@ -826,10 +884,10 @@ def main():
                     pass
     else:
         out['cpu_baseline'] = None
-        out['cpu_baseline_note'] = ('disabled by --no-cpu-baseline' if args.no_cpu_baseline else
+        out['cpu_baseline_note'] = ('runs with --full' if not args.full else 'disabled by --no-cpu-baseline' if args.no_cpu_baseline else
                                     'only timed on rank 0 of a 1-GPU run' if world != 1 else
                                     'the CPU oracle legs are implemented for the train workload (oracle optimize_parameters) and the infer workload (oracle inference DAG)')
-    if rank == 0 and world == 1 and args.workload == 'train' and not dry and not args.no_other_workloads and (n, s, args.ngf) == (8, 512, 64):
+    if args.full and rank == 0 and world == 1 and args.workload == 'train' and not dry and not args.no_other_workloads and (n, s, args.ngf) == (8, 512, 64):
         torch.cuda.empty_cache()
         out['other_workloads'] = other_workloads(args)
     if rank == 0:

@@ -1,6 +1,58 @@
 """Helpers shared by make_golden.py (fixture writer) and the tests (fixture readers)."""
+import glob
+import io
+import os
+
 import numpy as np
 import torch
+
+PART_BYTES = 900 << 10      # a committed fixture file stays below 1 MiB: a larger fixture is written as <name>.npz + <name>.<i>.npz
+
+
+def save_npz(path, arrays):
+    """np.savez_compressed of `arrays` at `path` (<name>.npz), split by arrays into parts of at most PART_BYTES compressed (load_npz joins them)"""
+    stem = path[:-len('.npz')]
+    for old in glob.glob(stem + '.[0-9]*.npz'):
+        os.remove(old)
+    parts, cur, size = [], {}, 0
+    for k, v in arrays.items():
+        buf = io.BytesIO()
+        np.savez_compressed(buf, **{k: v})
+        n = buf.getbuffer().nbytes
+        if cur and size + n > PART_BYTES:
+            parts.append(cur)
+            cur, size = {}, 0
+        cur[k] = v
+        size += n
+    parts.append(cur)
+    for i, part in enumerate(parts):
+        np.savez_compressed(path if i == 0 else f'{stem}.{i}.npz', **part)
+
+
+class _Fixture:
+    """the arrays of <name>.npz and its parts, read like the NpzFile of one file (`.files`, `[key]`, `in`)"""
+
+    def __init__(self, paths):
+        self._parts = [np.load(p) for p in paths]
+        self._where = {k: z for z in self._parts for k in z.files}
+        self.files = [k for z in self._parts for k in z.files]
+
+    def __getitem__(self, k):
+        return self._where[k][k]
+
+    def __contains__(self, k):
+        return k in self._where
+
+    def keys(self):
+        return list(self.files)
+
+
+def load_npz(path):
+    """the fixture save_npz wrote at `path`: <name>.npz followed by <name>.1.npz, <name>.2.npz, ..."""
+    stem, paths = path[:-len('.npz')], [path]
+    while os.path.exists(f'{stem}.{len(paths)}.npz'):
+        paths.append(f'{stem}.{len(paths)}.npz')
+    return _Fixture(paths)
 
 
 def seeded_uniform(shape, seed):

@@ -22,7 +22,7 @@ ROOT = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, HERE)
 sys.path.insert(0, ROOT)
 import _ref_import  # noqa: E402
-from golden_util import digest, seeded_uniform  # noqa: E402
+from golden_util import digest, save_npz, seeded_uniform  # noqa: E402
 from oracle import deepliif_oracle as O  # noqa: E402
 
 models, networks = _ref_import.import_reference()
@@ -85,7 +85,7 @@ def make_nets_small():
     seed += 2
     net = networks.define_D(12, 8, 'n_layers', 4, 'batch', 'normal', 0.02, [])
     net_case('n_layers_in12_batch', net, ('n_layers', 12, 8, 'batch', 'zero', seed), seed + 1, (1, 12, 64, 64), out)
-    np.savez_compressed(os.path.join(HERE, 'nets_small.npz'), **out)
+    save_npz(os.path.join(HERE, 'nets_small.npz'), out)
     print('nets_small.npz', len(out), 'arrays')
 
 
@@ -302,7 +302,7 @@ def make_inference():
         for k, v in res.items():
             out[f'tile{t}/{k}'] = v.numpy()
     out['keys'] = np.array(list(res.keys()))
-    np.savez_compressed(os.path.join(HERE, 'inference_small.npz'), **out)
+    save_npz(os.path.join(HERE, 'inference_small.npz'), out)
     print('inference_small.npz', list(res.keys()))
 
 

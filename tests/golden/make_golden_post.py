@@ -21,7 +21,7 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 from _ref_import import install_stubs          # noqa: E402
-from golden_util import synth_cells            # noqa: E402
+from golden_util import save_npz, synth_cells  # noqa: E402
 
 CASES = [
     # name, (H, W), seed, n_cells, kwargs of compute_final_results
@@ -105,7 +105,7 @@ def main():
         names.append(name)
         print(name, 'cells', len(cells), 'scoring', scoring, '== metrics.json', metrics[n])
     out['names'] = np.array(names)
-    np.savez_compressed(os.path.join(HERE, 'post_cases.npz'), **out)
+    save_npz(os.path.join(HERE, 'post_cases.npz'), out)
 
 
 if __name__ == '__main__':

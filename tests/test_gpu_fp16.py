@@ -23,7 +23,7 @@ from deepliif_amd import networks as N
 from deepliif_amd import ops
 from deepliif_amd.engine import Precision
 from deepliif_amd.geometry import ConvSpec, cpad, fill_conv_desc
-from golden_util import seeded_uniform
+from golden_util import load_npz, seeded_uniform
 from oracle import deepliif_oracle as O
 
 from test_gpu_kernels import _run_conv
@@ -297,7 +297,7 @@ def test_reference_run_dask_fixture_on_the_fp16_policy():
         pytest.skip('GPU policy comparison')
     import numpy as np
     from deepliif_amd import inference as I
-    z = np.load(os.path.join(os.path.dirname(__file__), 'golden', 'inference_small.npz'))
+    z = load_npz(os.path.join(os.path.dirname(__file__), 'golden', 'inference_small.npz'))
     opt = types.SimpleNamespace(model='DeepLIIF', modalities_no=4, seg_gen=True, mod_id_seg='S', input_id=0, input_nc=3, output_nc=3, ngf=8,
                                 norm='batch', padding='zero', net_g='resnet_9blocks', net_gs='unet_64', input_no=1,
                                 modalities_names=['IHC', 'Hema', 'DAPI', 'Lap2', 'Marker'], gpu_ids=[0])

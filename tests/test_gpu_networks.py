@@ -29,7 +29,7 @@ from deepliif_amd import engine as E
 from deepliif_amd import models as M
 from deepliif_amd import networks as N
 from deepliif_amd import ops
-from golden_util import digest_close, seeded_uniform
+from golden_util import digest_close, load_npz, seeded_uniform
 from oracle import deepliif_oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -176,7 +176,7 @@ def test_inference_golden_fixture_from_reference():
     """run_dask on the fixture produced by the REFERENCE's run_dask (tests/golden/inference_small.npz): three tiles in
     one batch must each equal the reference's single-tile outputs (per-sample normalisation)."""
     from deepliif_amd import inference as I
-    z = np.load(os.path.join(G, 'inference_small.npz'))
+    z = load_npz(os.path.join(G, 'inference_small.npz'))
     opt = types.SimpleNamespace(model='DeepLIIF', modalities_no=4, seg_gen=True, mod_id_seg='S', input_id=0, input_nc=3, output_nc=3, ngf=8,
                                 norm='batch', padding='zero', net_g='resnet_9blocks', net_gs='unet_64', input_no=1,
                                 modalities_names=['IHC', 'Hema', 'DAPI', 'Lap2', 'Marker'], gpu_ids=[0])

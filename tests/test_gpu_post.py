@@ -9,11 +9,11 @@ import torch
 
 from deepliif_amd import ops
 from deepliif_amd import postprocessing as PP
-from golden_util import synth_cells
+from golden_util import load_npz, synth_cells
 from oracle import postprocess_oracle as PO
 
 pytestmark = pytest.mark.gpu
-Z = np.load(os.path.join(os.path.dirname(__file__), 'golden', 'post_cases.npz'))
+Z = load_npz(os.path.join(os.path.dirname(__file__), 'golden', 'post_cases.npz'))
 NAMES = [str(n) for n in Z['names']]
 
 

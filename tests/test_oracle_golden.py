@@ -7,7 +7,7 @@ import numpy as np
 import pytest
 import torch
 
-from golden_util import digest, digest_close, seeded_uniform
+from golden_util import digest, digest_close, load_npz, seeded_uniform
 from oracle import deepliif_oracle as O
 
 G = os.path.join(os.path.dirname(__file__), 'golden')
@@ -24,7 +24,7 @@ def _cases(npz):
     return sorted({k.split('/')[0] for k in npz.files if '/meta' in k})
 
 
-NETS = np.load(os.path.join(G, 'nets_small.npz'))
+NETS = load_npz(os.path.join(G, 'nets_small.npz'))
 
 
 def _run(arch, sd, x, norm, pad, update_running=False):
@@ -136,7 +136,7 @@ def test_two_step_trajectory(tag):
 
 def test_inference_dag():
     """run_dask equivalent: G_i(tile), GS_0(tile), GS_i(G_i(tile)), seg = sum w_i seg_i  (models/__init__.py:293-338)."""
-    z = np.load(os.path.join(G, 'inference_small.npz'))
+    z = load_npz(os.path.join(G, 'inference_small.npz'))
     nets = {}
     for name, seed in zip(z['net_names'], z['net_seeds']):
         name = str(name)

@@ -6,8 +6,9 @@ import numpy as np
 import pytest
 
 from deepliif_amd import postprocessing as PP
+from golden_util import load_npz
 
-Z = np.load(os.path.join(os.path.dirname(__file__), 'golden', 'post_cases.npz'))
+Z = load_npz(os.path.join(os.path.dirname(__file__), 'golden', 'post_cases.npz'))
 NAMES = [str(n) for n in Z['names']]
 
 

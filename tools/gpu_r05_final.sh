@@ -5,6 +5,7 @@
 TAG=${1:-r05}
 export TMPDIR=/tmp
 mkdir -p gpurun_out
+OUT=$_    # the results folder
 if [ "$2" != "notests" ]; then
 timeout 1800 python -m pytest tests -m gpu -q --timeout=900 > gpurun_out/gpu_tests_$TAG.log 2>&1; echo "tests rc=$?"; grep -E "passed|failed|^FAILED|^ERROR" gpurun_out/gpu_tests_$TAG.log | tail -12
 cp gpurun_out/parity_errors.json gpurun_out/parity_errors_main_$TAG.json 2>/dev/null
@@ -12,7 +13,7 @@ cp gpurun_out/parity_errors_fullsize.json gpurun_out/parity_errors_fullsize_$TAG
 cp gpurun_out/parity_errors_fullsize_step.json gpurun_out/parity_errors_fullsize_step_$TAG.json 2>/dev/null
 timeout 300 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -1
 fi
-timeout 1200 python bench.py --gpus 1 --steps 20 --warmup 5 > gpurun_out/bench_contract_$TAG.json 2> gpurun_out/bench_contract_$TAG.err; echo "contract bench rc=$?"
+timeout 1200 python bench.py --gpus 1 --steps 20 --warmup 5 --full > "$OUT/bench_contract_$TAG.json" 2> "$OUT/bench_contract_$TAG.err"; echo "contract bench rc=$?"
 python - <<PY
 import json
 d = json.loads(open('gpurun_out/bench_contract_$TAG.json').read().strip().splitlines()[-1])

@@ -5,6 +5,7 @@
 TAG=${1:-r06}
 export TMPDIR=/tmp
 mkdir -p gpurun_out
+OUT=$_    # the results folder
 if [ "$2" != "notests" ]; then
 timeout 2700 python -m pytest tests -m gpu -q --timeout=1200 > gpurun_out/gpu_tests_$TAG.log 2>&1; echo "tests rc=$?"; grep -E "passed|failed|^FAILED|^ERROR" gpurun_out/gpu_tests_$TAG.log | tail -12
 cp gpurun_out/parity_errors.json gpurun_out/parity_errors_main_$TAG.json 2>/dev/null
@@ -13,7 +14,7 @@ cp gpurun_out/parity_errors_fullsize_step.json gpurun_out/parity_errors_fullsize
 cp gpurun_out/trajectory.json gpurun_out/trajectory_$TAG.json 2>/dev/null
 timeout 300 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -1
 fi
-timeout 1200 python bench.py --gpus 1 --steps 20 --warmup 5 > gpurun_out/bench_contract_$TAG.json 2> gpurun_out/bench_contract_$TAG.err; echo "contract bench rc=$?"
+timeout 1200 python bench.py --gpus 1 --steps 20 --warmup 5 --full > "$OUT/bench_contract_$TAG.json" 2> "$OUT/bench_contract_$TAG.err"; echo "contract bench rc=$?"
 python - <<PY
 import json
 d = json.loads(open('gpurun_out/bench_contract_$TAG.json').read().strip().splitlines()[-1])
@@ -38,6 +39,6 @@ PY
 done
 timeout 600 python tools/layer_budget.py $TAG bf16 2>&1 | tail -26
 if [ "$3" != "nocpu" ]; then
-timeout 1500 python bench.py --steps 3 --warmup 1 --no-strict --no-graph --no-timer-check --no-other-workloads --cpu-baseline-n8-full > gpurun_out/bench_n8full_$TAG.json 2>/dev/null; cat gpurun_out/cpu_baseline_n8_full.json
+timeout 1500 python bench.py --steps 3 --warmup 1 --full --no-strict --no-graph --no-timer-check --no-other-workloads --cpu-baseline-n8-full > "$OUT/bench_n8full_$TAG.json" 2>/dev/null; cat "$OUT/cpu_baseline_n8_full.json"
 timeout 500 python tools/dp_host_load.py 2>&1 | tail -3
 fi

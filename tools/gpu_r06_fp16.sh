@@ -12,7 +12,7 @@ if [ "$2" != "nobench" ]; then
 for p in bf16 fp16; do
   for wl in infer wsi; do
     echo "== bench --workload $wl --precision $p" >> $O
-    timeout 900 python bench.py --workload $wl --precision $p --steps 5 --warmup 2 --no-cpu-baseline --no-timer-check 2>/dev/null | tail -1 > gpurun_out/fp16_bench_${wl}_${p}.json
+    timeout 900 python bench.py --workload $wl --precision $p --steps 5 --warmup 2 --full --no-cpu-baseline --no-timer-check 2>/dev/null | tail -1 > "${O%/*}/fp16_bench_${wl}_${p}.json"
     python -c "
 import json; d=json.loads(open('gpurun_out/fp16_bench_${wl}_${p}.json').read()); r=d.get('roofline') or {}
 print(d['value'], 'tiles/s', d['ms_per_step'], 'ms', d['dtype'], r.get('kernel'), r.get('avg_launch_us'), r.get('frac'))

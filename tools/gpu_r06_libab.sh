@@ -24,7 +24,7 @@ for i, r in enumerate(rows):
     if i < 14 or any(t in r['Name'] for t in show):
         print('  %-70s %5s calls %8.1f us avg' % (r['Name'][:70], r['Calls'], float(r['AverageNs']) / 1e3))
 PY
-  timeout 300 python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-cpu-baseline-n8 --no-strict --no-timer-check --no-other-workloads 2>/dev/null | tail -1 > gpurun_out/libab_bench.json
+  timeout 300 python bench.py --steps 10 --warmup 3 --full --no-cpu-baseline --no-cpu-baseline-n8 --no-strict --no-timer-check --no-other-workloads 2>/dev/null | tail -1 > "${O%/*}/libab_bench.json"
   python -c "
 import json; d=json.loads(open('gpurun_out/libab_bench.json').read()); r=d['roofline']; print('$v tiles/s', d['value'], 'ms', d['ms_per_step'], 'one-stream', r.get('one_stream_ms_per_step'), 'w4 us', r.get('avg_launch_us'))" >> $O
 done

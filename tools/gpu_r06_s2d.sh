@@ -15,7 +15,7 @@ done
 if [ "$2" != "nosteps" ]; then
 echo "== whole steps (DL_CONV_S2D)" >> $O
 for v in 0 1 0 1; do
-  DL_CONV_S2D=$v timeout 300 python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-cpu-baseline-n8 --no-strict --no-timer-check --no-other-workloads 2>/dev/null | tail -1 > gpurun_out/s2d_bench_$v.json
+  DL_CONV_S2D=$v timeout 300 python bench.py --steps 10 --warmup 3 --full --no-cpu-baseline --no-cpu-baseline-n8 --no-strict --no-timer-check --no-other-workloads 2>/dev/null | tail -1 > "${O%/*}/s2d_bench_$v.json"
   python -c "
 import json; d=json.loads(open('gpurun_out/s2d_bench_$v.json').read()); r=d['roofline']; print('S2D=$v', d['value'], d['ms_per_step'], r['avg_launch_us'], r['frac'], r.get('one_stream_ms_per_step'))" >> $O
 done
