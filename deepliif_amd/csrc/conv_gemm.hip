@@ -1771,19 +1771,45 @@ static int glds_tile_bm(const dl_conv_desc *d) {
     return 128;
 }
 
-// Name of the kernel dl_conv_forward launches for this descriptor (as rocprofv3 prints it, without template noise); lets the
-// benchmark label its roofline line from the dispatch itself instead of a string that goes stale when a default changes.
+// THE routing of dl_conv_forward and its siblings: which special kernel takes this descriptor, ROUTE_TILE = none (the tile dispatch: gather GEMMs, w4, 8ph ...).
+// Both the launch (conv_forward_impl) and the name (dl_conv_kernel_name) are derived from this one function, so they cannot drift apart.  It decides on the
+// DESCRIPTOR alone (a bias is d->bias_n > 0; conv_forward_impl brings the pointer in line with that before anything else looks at it) plus the three per-call
+// facts the descriptor cannot carry: fused norm-backward reductions (dl_conv_forward_bnstats), fused statistics (stats_part), a fused addend (dl_conv_forward_add).
+enum ConvRoute { ROUTE_DOT_FWD, ROUTE_DOT_DGRAD, ROUTE_C4, ROUTE_D1, ROUTE_D1G, ROUTE_C4_X3, ROUTE_S2U, ROUTE_S2F, ROUTE_S2F_X3, ROUTE_S2D, ROUTE_TILE };
+
+static ConvRoute conv_route(const dl_conv_desc *d, bool bn, bool stats, bool add) {
+    const bool plain = !bn && !stats && !add;
+    if (plain) {
+        if (const int k = dot_applies(d)) return k == 1 ? ROUTE_DOT_FWD : ROUTE_DOT_DGRAD;      // (no split-K, whatever the descriptor says: nothing to reduce)
+    }
+    if (c4_bf16_eligible(d)) return ROUTE_C4;
+    if (plain && d1_applies(d)) return ROUTE_D1;
+    if (plain && d1g_applies(d)) return ROUTE_D1G;
+    if (c4_x3_eligible(d)) return ROUTE_C4_X3;
+    if (!bn && s2u_applies(d)) return ROUTE_S2U;
+    if (!bn && s2f_applies(d)) return ROUTE_S2F;
+    if (!bn && s2fx3_applies(d)) return ROUTE_S2F_X3;
+    if (!bn && s2d_applies(d)) return ROUTE_S2D;
+    return ROUTE_TILE;
+}
+
+// Name of the kernel a plain dl_conv_forward (no fused statistics / reductions / addend) launches for this descriptor (as rocprofv3 prints it, without template
+// noise): conv_route(), then the tile dispatch's own rules.  Lets the benchmark label its roofline line from the dispatch itself instead of a string that goes stale.
 extern "C" const char *dl_conv_kernel_name(const dl_conv_desc *d) {
     if (!d) return "(null)";
-    if (c4_bf16_eligible(d)) return "conv_c4_patch_kernel";
-    if (c4_x3_eligible(d)) return "conv_c4_patch_x3_kernel";
-    if (const int k = dot_applies(d)) return k == 1 ? "conv_dot_fwd_kernel" : "conv_dot_dgrad_kernel";
-    if (d1_applies(d)) return "conv_d1_kernel";
-    if (d1g_applies(d)) return "conv_d1g_kernel";
-    if (s2u_applies(d)) return "conv_s2u_kernel";
-    if (s2f_applies(d)) return "conv_s2f_kernel";
-    if (s2d_applies(d)) return "conv_s2d_kernel";
-    if (s2fx3_applies(d)) return "conv_s2f_x3_kernel";
+    switch (conv_route(d, false, false, false)) {
+    case ROUTE_DOT_FWD: return "conv_dot_fwd_kernel";
+    case ROUTE_DOT_DGRAD: return "conv_dot_dgrad_kernel";
+    case ROUTE_C4: return "conv_c4_patch_kernel";
+    case ROUTE_D1: return "conv_d1_kernel";
+    case ROUTE_D1G: return "conv_d1g_kernel";
+    case ROUTE_C4_X3: return "conv_c4_patch_x3_kernel";
+    case ROUTE_S2U: return "conv_s2u_kernel";
+    case ROUTE_S2F: return "conv_s2f_kernel";
+    case ROUTE_S2F_X3: return "conv_s2f_x3_kernel";
+    case ROUTE_S2D: return "conv_s2d_kernel";
+    case ROUTE_TILE: break;
+    }
     const int bm = glds_tile_bm(d);
     if (bm == 0 && x3_glds_applies(d)) {
         if (w4x3_enabled()) {
@@ -1896,6 +1922,8 @@ static int conv_forward_impl(const dl_conv_desc *d, const void *in, const void *
         DL_FAIL("dl_conv_forward: empty problem (N=%d, in %dx%d, out %dx%d, phase grid %dx%d): nothing to launch", d->N, d->Hi, d->Wi, d->Ho,
                 d->Wo, d->Hq, d->Wq);
     if (!in || !w_hi || (!out && !d->raw_out)) DL_FAIL("dl_conv_forward: null argument");
+    if (d->bias_n < 0 || (d->bias_n > 0 && !bias)) DL_FAIL("dl_conv_forward: bias_n=%d without a bias", d->bias_n);
+    if (d->bias_n == 0) bias = nullptr;          // a bias POINTER without entries is no bias: the routing (conv_route) and every kernel see one fact, not two
     const int l2 = ilog2_exact(d->Ci);
     if (l2 < 3) DL_FAIL("dl_conv_forward: Ci=%d must be a power of two >= 8", d->Ci);
     if (d->Co % 8 || d->Co <= 0) DL_FAIL("dl_conv_forward: Co=%d must be a positive multiple of 8", d->Co);
@@ -1942,19 +1970,16 @@ static int conv_forward_impl(const dl_conv_desc *d, const void *in, const void *
 
     int rc;
     static const bool no_glds = DL_DEV_ENV("DL_NO_GLDS") != nullptr;      // A/B switch for profiling the two staging paths
-    if (!bn && !stats_part && !add) {
-        if (const int k = dot_applies(d)) {
-            if (k == 1 ? dot_fwd_eligible(a) : dot_dgrad_eligible(a)) return launch_conv_dot(a, k == 1, stream);     // (no split-K, whatever the descriptor says: nothing to reduce)
-        }
-    }
-    if (c4_bf16_eligible(d)) rc = launch_conv_c4(a, d, stream);
-    else if (!bn && !stats_part && !add && d1_applies(d)) rc = launch_conv_d1(a, stream);
-    else if (!bn && !stats_part && !add && !bias && d1g_applies(d)) rc = launch_conv_d1g(a, stream);
-    else if (c4_x3_eligible(d)) rc = launch_conv_c4_x3(a, d, stream);
-    else if (!bn && s2u_applies(d)) rc = launch_conv_s2u(a, stream);
-    else if (!bn && s2f_applies(d)) rc = launch_conv_s2f(a, stream);
-    else if (!bn && s2fx3_applies(d)) rc = launch_conv_s2f_x3(a, stream);
-    else if (!bn && s2d_applies(d)) rc = launch_conv_s2d(a, stream);
+    const ConvRoute route = conv_route(d, bn != nullptr, stats_part != nullptr, add != nullptr);
+    if (route == ROUTE_DOT_FWD || route == ROUTE_DOT_DGRAD) return launch_conv_dot(a, route == ROUTE_DOT_FWD, stream);
+    if (route == ROUTE_C4) rc = launch_conv_c4(a, d, stream);
+    else if (route == ROUTE_D1) rc = launch_conv_d1(a, stream);
+    else if (route == ROUTE_D1G) rc = launch_conv_d1g(a, stream);
+    else if (route == ROUTE_C4_X3) rc = launch_conv_c4_x3(a, d, stream);
+    else if (route == ROUTE_S2U) rc = launch_conv_s2u(a, stream);
+    else if (route == ROUTE_S2F) rc = launch_conv_s2f(a, stream);
+    else if (route == ROUTE_S2F_X3) rc = launch_conv_s2f_x3(a, stream);
+    else if (route == ROUTE_S2D) rc = launch_conv_s2d(a, stream);
     else if (d->in_dtype == DL_BF16 && d->prec == DL_PREC_BF16 && d->in_act == DL_ACT_NONE && !no_glds) rc = dispatch_tile_glds(a, stream);
     else if (d->in_dtype == DL_BF16 && d->prec == DL_PREC_BF16) rc = dispatch_tile<bf16_t, bf16_t, 1>(a, stream);
     else if (d->in_dtype == DL_F32 && d->prec == DL_PREC_BF16X3) rc = x3_glds_applies(d) ? dispatch_tile_x3(a, stream) : dispatch_tile<float, float, 3>(a, stream);

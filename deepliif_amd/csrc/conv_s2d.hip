@@ -315,6 +315,7 @@ bool s2d_eligible(const ConvArgs &a) {
     if (a.Hi != 2 * a.Ho || a.Wi != 2 * a.Wo || a.Hq != a.Ho || a.Wq != a.Wo || (a.Wo & 127) || (a.Ho & 1)) return false;
     if (a.pad_mode != DL_PAD_ZERO || a.bn_y != nullptr || a.in_act != DL_ACT_NONE || a.epi_old) return false;
     if (a.act != DL_ACT_NONE && a.act != DL_ACT_RELU) return false;
+    if ((size_t)a.Hi * a.Wi * (size_t)a.in_pstride * 2 >= ((size_t)1 << 31) || (size_t)a.Ho * a.Wo * (size_t)a.out_pstride * 2 >= ((size_t)1 << 31)) return false;      // 32-bit offsets
     for (int t = 0; t < 9; ++t) {
         const int dh = (int)(int8_t)(a.taps[t] & 0xff), dw = (int)(int8_t)((a.taps[t] >> 8) & 0xff);
         if (dh != t / 3 - 1 || dw != t % 3 - 1) return false;

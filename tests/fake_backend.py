@@ -108,6 +108,7 @@ class FakeBackend:
         if bias is not None:
             acc[..., :bias.numel()] += bias.float()
         out.copy_(_act(act, acc).to(out.dtype))
+        return 0            # chunks of fused statistics (want_stats / bn): none, the caller's normalisation makes its own pass
 
     def conv_wgrad(self, P, Q, grad, k, step, pad, pad_mode, p_act, q_act, prec, accumulate, splitk=None, stack_kw=0, p_split=False, q_split=False):
         self._count('wgrad')
