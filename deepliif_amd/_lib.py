@@ -20,7 +20,7 @@ NORM_INSTANCE, NORM_BATCH = 0, 1
 LOSS_BCE_LOGITS, LOSS_MSE, LOSS_SMOOTH_L1, LOSS_L1, LOSS_LINEAR = 0, 1, 2, 3, 4
 MAX_TAPS, MAX_PHASES = 64, 4
 WGRAD_MULTI_MAX = 24
-DL_VERSION = 114
+DL_VERSION = 115
 
 i32 = C.c_int32
 
@@ -103,6 +103,12 @@ SIGNATURES = {
     'dl_pack_job_fill': (_i, [C.POINTER(PackDesc), _vp, _vp, _vp, _vp]),
     'dl_pack_batch_blocks': (_i, [_vp, _i, _vp]),
     'dl_pack_weights_batch': (_i, [_vp, _vp, _i, _vp]),
+    'dl_spectral_job_bytes': (C.c_size_t, []),
+    'dl_spectral_scratch_floats': (C.c_size_t, [_i, _i]),
+    'dl_spectral_job_fill': (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    'dl_spectral_blocks': (_i, [_vp, _i, _i, _vp]),
+    'dl_spectral_forward': (_i, [_vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp]),
+    'dl_spectral_backward': (_i, [_vp, _i, _vp, _i, _vp, _i, _vp]),
     'dl_norm_ws_floats': (C.c_size_t, [C.POINTER(NormDesc)]),
     'dl_norm_forward': (_i, [C.POINTER(NormDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'dl_norm_backward': (_i, [C.POINTER(NormDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),

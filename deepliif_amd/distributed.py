@@ -76,7 +76,10 @@ class GradExchanger:
     param_final(p)             (Tape.on_final) one parameter's gradient is final: networks above 64 MB send their final tail in 32 MB buckets
     ready(params)              the gradients of this contiguous run of parameters are final: exchange what has not gone out yet (asynchronously)
     finish(optimizer)          exchange whatever was not announced, wait for everything, set optimizer.dp_scale
-    all_reduce(optimizer)      begin + finish without announcements (one blocking exchange)"""
+    all_reduce(optimizer)      begin + finish without announcements (one blocking exchange)
+
+    Only gradients travel.  The _u / _v buffers of spectrally normalised nets (engine.SpectralSet) are NOT exchanged: ranks start from identical weights and
+    buffers (sync_parameters), every rank applies the same averaged update, and the power-iteration kernels are deterministic, so the buffers stay equal."""
 
     def __init__(self):
         self.handles: List = []

@@ -9,6 +9,7 @@ Precision policies:
 from __future__ import annotations
 
 import os
+import threading
 import weakref
 
 from dataclasses import dataclass
@@ -115,6 +116,8 @@ class Tape:
         # branch streams (models.BaseModel._branch): every node remembers the HIP stream it was recorded on and runs its backward there -- a
         # branch's forward, its losses and its backward stay in one in-order stream, different branches overlap on the GPU
         self.node_streams: Optional[list] = [] if streams else None
+        # (SpectralSet, generation) of every spectrally normalised forward call recorded here: handed back when the tape is released
+        self.held: list = []
 
     def record(self, fn: Callable[[], None]):
         self.nodes.append(fn)
@@ -167,6 +170,19 @@ class Tape:
         finally:
             if begin is not None:
                 be.wgrad_defer_end()
+            self.release()
+
+    def release(self):
+        """the recorded pass is over (or abandoned): its spectral generations go back to their pools"""
+        held, self.held = self.held, []
+        for sset, gen in held:
+            sset.give_back(gen)
+
+    def __del__(self):
+        try:
+            self.release()
+        except Exception:
+            pass
 
 
 def settle_gc():
@@ -218,17 +234,24 @@ LAYER_OF_WEIGHT: 'weakref.WeakValueDictionary[int, ConvLayer]' = weakref.WeakVal
 class ConvLayer:
     """One Conv2d / ConvTranspose2d of the reference networks bound to its nn.Parameter(s)."""
 
-    def __init__(self, spec: ConvSpec, weight: torch.nn.Parameter, bias: Optional[torch.nn.Parameter]):
+    def __init__(self, spec: ConvSpec, weight: torch.nn.Parameter, bias: Optional[torch.nn.Parameter], spectral_norm: Optional[torch.nn.Module] = None):
         self.spec = spec
         self.weight = weight
         self.bias = bias
+        self.tape_weight = weight           # what conv() announces to Tape.use / done
+        # spectral normalisation: `weight` is parametrizations.weight.original, `sn` the _SpectralNorm module (buffers _u, _v); the weight a forward call
+        # convolves with belongs to a generation of the SpectralSet this layer joins (conv() asks `spectral` for the calling thread's view of the layer)
+        self.sn = spectral_norm
+        self.spectral: Optional['SpectralSet'] = None
+        self.sidx = -1
         self.fwd_plan = spec.forward_plan()
         self._dgrad_plan = None
         self.packed_fwd: Optional[ops.PackedWeights] = None
         self.packed_dgrad: Optional[ops.PackedWeights] = None
         self.fwd_key = None
         self.dgrad_key = None
-        LAYER_OF_WEIGHT[id(weight)] = self
+        if spectral_norm is None:           # (a spectral layer's images are rebuilt by every training forward: PackBatch has nothing to repack)
+            LAYER_OF_WEIGHT[id(weight)] = self
         # narrow-Cout layers (the 7x7, 64 -> 3 ResnetGenerator head): kernel columns folded into the GEMM rows (dl_shift_sum)
         self.narrow = spec.is_narrow()
         if self.narrow:
@@ -305,6 +328,199 @@ class PackBatch:
         return len(jobs)
 
 
+class _GenWeight:
+    """what conv() reads of a weight, for a spectral layer's view: requires_grad of the master weight at the time of the call and, as `.grad`, the
+    generation's buffer for the gradient with respect to the EFFECTIVE weight"""
+    __slots__ = ('requires_grad', 'grad')
+
+    def __init__(self, requires_grad, grad):
+        self.requires_grad, self.grad = requires_grad, grad
+
+
+class GenConv:
+    """One spectral ConvLayer as ONE forward call sees it: geometry of the layer, weight / images / gradient buffer of the call's generation."""
+
+    def __init__(self, base: ConvLayer):
+        self.spec, self.bias, self.fwd_plan, self.narrow = base.spec, base.bias, base.fwd_plan, base.narrow
+        self.spectral = None
+        self.tape_weight = None             # the master weight's gradient is final after SpectralSet's fold node, not after this layer's weight gradient
+        self.weight: Optional[_GenWeight] = None
+        self.packed_fwd: Optional[ops.PackedWeights] = None
+        self.packed_dgrad: Optional[ops.PackedWeights] = None
+
+    def ensure_packed(self, prec: Precision, need_dgrad: bool):
+        assert self.packed_fwd is not None and (self.packed_dgrad is not None or not need_dgrad), 'SpectralSet.begin packs the images of a call'
+
+
+class SpectralGeneration:
+    """Everything ONE forward call of a spectrally normalised network leaves behind for its convolutions and its backward: the fp32 effective weights
+    W / sigma, the u, v, sigma of the call, the buffers its weight-gradient kernels write (gradient w.r.t. the effective weight) and the GEMM images packed
+    from the effective weights.  Flat buffers, one slice per layer (each 16-byte aligned)."""
+
+    def __init__(self, sset: 'SpectralSet'):
+        dev = sset.layers[0].weight.device
+        self.device = dev
+        self.weff_flat = torch.empty(sset.w_total, dtype=torch.float32, device=dev)
+        self.g_flat: Optional[torch.Tensor] = None          # allocated by the first call that records a tape
+        self.uv_flat = torch.empty(sset.uv_total, dtype=torch.float32, device=dev)
+        self.sigma = torch.empty(len(sset.layers), dtype=torch.float32, device=dev)
+        self.weff = [self.weff_flat[o:o + l.weight.numel()].view(l.weight.shape) for l, o in zip(sset.layers, sset.w_off)]
+        self.g: Optional[list] = None
+        self.views = [GenConv(l) for l in sset.layers]
+        self.images = {}                                    # (layer, 'fwd' | 'dgrad', with_lo, half) -> PackedWeights
+        self.pack_tables = {}
+        self.table, self.table_sig = None, None
+        self.key = None                                     # eval cache only
+
+    def need_g(self, sset: 'SpectralSet'):
+        if self.g_flat is None:
+            self.g_flat = torch.empty(sset.w_total, dtype=torch.float32, device=self.device)
+            self.g = [self.g_flat[o:o + l.weight.numel()].view(l.weight.shape) for l, o in zip(sset.layers, sset.w_off)]
+
+
+class SpectralSet:
+    """The spectrally normalised conv layers of ONE network (`--norm spectral`; torch.nn.utils.parametrizations._SpectralNorm is the specification).
+    begin(ctx) is the first thing the network's run() does:
+      * a module in train() mode runs one power iteration per forward call of the network, whether or not its parameters are frozen and whether or not a
+        tape records -- a discriminator called on the fake pairs, on the real pairs and again by the generator pass moves u, v three times and has three sigmas;
+      * every such call (and every call recorded on a tape) takes a GENERATION from a small pool: dl_spectral_forward fills it, one batched pack launch builds
+        its GEMM images, the call's conv nodes use them for forward and data gradient and write their weight gradients into the generation; a tape node
+        recorded IN FRONT of the call's nodes -- reverse mode reaches it behind them -- folds those into parametrizations.weight.original.grad with ONE
+        dl_spectral_backward, using the u, v, sigma of that call.  The generation returns to the pool when the tape is released;
+      * an eval() forward without a tape iterates nothing: effective weights and images are cached, keyed like ConvLayer.ensure_packed plus the versions of
+        the buffers, so serving pays a key comparison per forward and nothing per tile.
+    Ranks of a data-parallel run start from identical weights and u, v and the kernels are deterministic: the buffers are not exchanged."""
+
+    def __init__(self, layers):
+        self.layers = list(layers)
+        assert self.layers and all(l.sn is not None for l in self.layers)
+        self.w_off, self.uv_off = [], []
+        nw = nuv = 0
+        for i, l in enumerate(self.layers):
+            l.spectral, l.sidx = self, i
+            self.w_off.append(nw)
+            nw += (l.weight.numel() + 3) // 4 * 4
+            self.uv_off.append(nuv)
+            nuv += (l.sn._u.numel() + l.sn._v.numel() + 3) // 4 * 4
+        self.w_total, self.uv_total = nw, nuv
+        self.pool: list = []
+        self.eval_gen: Optional[SpectralGeneration] = None
+        self.uv_epoch = 0                   # bumped by every iterating call (the kernels write _u / _v through raw pointers: no torch version bump)
+        self._tls = threading.local()
+        self._lock = threading.Lock()
+
+    def view_of(self, layer: ConvLayer) -> GenConv:
+        gen = getattr(self._tls, 'gen', None)
+        assert gen is not None, 'a spectrally normalised layer ran outside its network (SpectralSet.begin was not called)'
+        return gen.views[layer.sidx]
+
+    def give_back(self, gen: SpectralGeneration):
+        if gen is not self.eval_gen and not any(gen is g for g in self.pool) and gen.device == self.layers[0].weight.device:
+            self.pool.append(gen)
+
+    def _iterating(self) -> bool:
+        modes = {bool(l.sn.training) for l in self.layers}
+        if len(modes) != 1:
+            raise NotImplementedError('spectral normalisation: the _SpectralNorm modules of one network are partly in train() and partly in eval() mode')
+        return modes.pop()
+
+    def _eval_key(self, prec: Precision):
+        ws = tuple((l.weight._version, l.weight.data_ptr(), getattr(l.weight, '_dl_epoch', 0), l.sn._u._version, l.sn._u.data_ptr(), l.sn._v._version,
+                    l.sn._v.data_ptr()) for l in self.layers)
+        return (ws, self.uv_epoch, prec.prec, prec.half, str(self.layers[0].weight.device))
+
+    def _transform(self, gen: SpectralGeneration, prec: Precision, iterate: bool, with_grad: bool, need_dgrad: bool):
+        be = ops.impl()
+        if with_grad:
+            gen.need_g(self)
+        jobs = []
+        for i, l in enumerate(self.layers):
+            w, sn = l.weight, l.sn
+            u0 = self.uv_off[i]
+            nu, nv = sn._u.numel(), sn._v.numel()
+            has_grad = with_grad and w.grad is not None
+            if with_grad and w.requires_grad and w.grad is None:
+                raise RuntimeError('a trainable spectrally normalised weight has no .grad buffer (optimizer.zero_grad() / p.grad = zeros first)')
+            jobs.append(ops.SpectralJob(w.detach(), sn.dim, sn._u, sn._v, gen.weff[i], gen.uv_flat[u0:u0 + nu], gen.uv_flat[u0 + nu:u0 + nu + nv],
+                                        gen.sigma[i:i + 1], gen.g[i] if has_grad else None, w.grad if has_grad else None))
+        sig = tuple(j.pointers() for j in jobs)
+        if sig != gen.table_sig:
+            gen.table, gen.table_sig = be.spectral_table(jobs), sig
+        if with_grad and any(l.weight.requires_grad for l in self.layers):
+            gen.g_flat.zero_()               # the weight-gradient kernels accumulate, as they do into a master weight's .grad
+        be.spectral_forward(gen.table, iterate)
+        if iterate:
+            self.uv_epoch += 1
+        # the GEMM images of the effective weights: one batched launch
+        with_lo = prec.prec == L.PREC_BF16X3
+        pkey = (prec.prec, prec.half, need_dgrad)
+        pt = gen.pack_tables.get(pkey)
+        for i, (l, v) in enumerate(zip(self.layers, gen.views)):
+            for kind in (('fwd', 'dgrad') if need_dgrad else ('fwd',)):
+                k = (i, kind, with_lo, prec.half)
+                if k not in gen.images:
+                    gen.images[k] = ops.PackedWeights(l.fwd_plan if kind == 'fwd' else l.dgrad_plan, gen.device, with_lo)
+                    pt = None
+            v.packed_fwd = gen.images[(i, 'fwd', with_lo, prec.half)]
+            v.packed_dgrad = gen.images.get((i, 'dgrad', with_lo, prec.half)) if need_dgrad else None
+            v.weight = _GenWeight(bool(l.weight.requires_grad), gen.g[i] if with_grad else None)
+        if pt is None:
+            pj = [(gen.images[(i, kind, with_lo, prec.half)], gen.weff[i]) for i in range(len(self.layers)) for kind in (('fwd', 'dgrad') if need_dgrad else ('fwd',))]
+            pt = gen.pack_tables[pkey] = (be.pack_batch_build(pj), len(pj))
+        be.pack_batch_run(*pt)
+
+    def begin(self, ctx: 'Ctx'):
+        """start of one forward call of the network (see the class docstring)"""
+        iterate = self._iterating()
+        dev = self.layers[0].weight.device
+        if ctx.tape is None and not iterate:
+            with self._lock:
+                key = self._eval_key(ctx.prec)
+                gen = self.eval_gen
+                if gen is None or gen.device != dev:
+                    gen = self.eval_gen = SpectralGeneration(self)
+                if gen.key != key:
+                    gen.key = None
+                    self._transform(gen, ctx.prec, False, False, False)
+                    gen.key = key
+            self._tls.gen = gen
+            return None
+        gen = None
+        while self.pool and gen is None:
+            gen = self.pool.pop()
+            if gen.device != dev:
+                gen = None
+        if gen is None:
+            gen = SpectralGeneration(self)
+        tape = ctx.tape
+        self._transform(gen, ctx.prec, iterate, tape is not None, tape is not None)
+        self._tls.gen = gen
+        if tape is None:
+            return gen                       # the caller hands it back when the call is over (end())
+        tape.held.append((self, gen))
+        trainable = tuple(i for i, l in enumerate(self.layers) if l.weight.requires_grad)
+        masters = [self.layers[i].weight for i in trainable]
+        tape.use(*masters)
+        be = ops.impl()
+
+        def fold():
+            try:
+                if trainable:
+                    flush = getattr(be, 'wgrad_flush', None)
+                    if flush is not None:
+                        flush()              # the call's deferred / queued weight gradients land in the generation first
+                    be.spectral_backward(gen.table, True, trainable)
+            finally:
+                tape.done(*masters)
+        tape.record(fold)
+        return None
+
+    def end(self, gen: Optional[SpectralGeneration]):
+        """a call without a tape is over: its kernels are queued in stream order, the generation can serve the next call"""
+        if gen is not None:
+            self.give_back(gen)
+
+
 class NormLayer:
     """BatchNorm2d-on-batch-statistics (affine, optional running-stat tracking) or InstanceNorm2d (no affine)."""
 
@@ -362,6 +578,8 @@ def conv(ctx: Ctx, x: Act, layer: ConvLayer, act: int = L.ACT_NONE, in_act: int 
     stats: the caller feeds y straight into ONE norm_act and into nothing else -- let the conv epilogue produce the norm statistics when
     it can, and let that norm's backward add sum(dy) to this conv's bias gradient (dy is then the only gradient y ever receives)."""
     be = ops.impl()
+    if layer.spectral is not None:
+        layer = layer.spectral.view_of(layer)       # this call's effective weight, images and gradient buffer (SpectralSet.begin)
     spec = layer.spec
     n, hi, wi, _ = x.t.shape
     ho, wo = spec.out_hw(hi, wi)
@@ -432,7 +650,7 @@ def conv(ctx: Ctx, x: Act, layer: ConvLayer, act: int = L.ACT_NONE, in_act: int 
         y.bias_grad = layer.bias.grad           # a following norm_act folds sum(dy) into its backward pass
 
     if w_needs:
-        ctx.tape.use(layer.weight, layer.bias)
+        ctx.tape.use(layer.tape_weight, layer.bias)
 
     def split_backward_ok(g_like: torch.Tensor, bias_done: bool) -> bool:
         """True if every consumer of dL/dy in backward_body() below reads the split copy (mirrors its branches one by one)"""
@@ -459,7 +677,7 @@ def conv(ctx: Ctx, x: Act, layer: ConvLayer, act: int = L.ACT_NONE, in_act: int 
             backward_body()
         finally:
             if w_needs:
-                ctx.tape.done(layer.weight, layer.bias)      # (also when no gradient arrived: this use contributes nothing more)
+                ctx.tape.done(layer.tape_weight, layer.bias)      # (also when no gradient arrived: this use contributes nothing more)
 
     def backward_body():
         g = y.grad

@@ -127,14 +127,15 @@ class _AttUNetT(nn.Module):
 def aten_twin(net: nn.Module) -> nn.Module:
     """Plain-torch module with the state_dict keys of `net` (and of the reference class it mirrors) and the reference's forward, holding
     CPU copies of the parameters.  The engine net is left untouched."""
-    bound = getattr(net, '_bound', None)
+    bound, spectral = getattr(net, '_bound', None), getattr(net, '_spectral', None)
     if bound is not None:
         net._bound = None               # bindings point at packed device buffers: not part of the module tree, not worth copying
+        net._spectral = None            # (the SpectralSet of a spectrally normalised net goes with its bindings)
     try:
         src = copy.deepcopy(net).cpu()
     finally:
         if bound is not None:
-            net._bound = bound
+            net._bound, net._spectral = bound, spectral
     if isinstance(src, N.ResnetGenerator):
         twin = _ResnetGeneratorT(src)
     elif isinstance(src, N.UnetGenerator):

@@ -81,6 +81,12 @@ def pick_gpu(gpu_ids, is_train: bool, env=None) -> int:
 _D_PAIR_BATCH = os.environ.get('DL_D_PAIR_BATCH', '1') != '0'
 
 
+def _pairable(d) -> bool:
+    """may a discriminator see the fake pairs and the real pairs as ONE batch?  Only if every sample is normalised on its own (no BatchNorm) and its weights
+    are the same for both calls (not spectrally normalised: the reference's two calls run two power iterations and divide by two sigmas)"""
+    return getattr(d, 'norm_kind', 'batch') != 'batch' and not getattr(d, 'spectral_norm', False)
+
+
 class StepGraph:
     """optimize_parameters() captured ONCE in a hipGraph and replayed per step: a training step is ~2 400 kernel launches issued
     by ~55 ms of Python for ~100 ms of GPU time; a replay is one launch.  The shapes are static, the losses stay on the device, the tape is
@@ -109,6 +115,9 @@ class StepGraph:
             self.why_eager = 'an optimizer other than FusedAdam'
         elif any(isinstance(m, torch.nn.Dropout) and m.training for _, net in model._nets() for m in net.modules()):
             self.why_eager = 'dropout is active (its seed is a kernel argument)'
+        elif any(getattr(net, 'spectral_norm', False) for _, net in model._nets()):
+            # the host picks a generation per forward call and keeps per-call state (engine.SpectralSet): not a fixed launch sequence
+            self.why_eager = "spectral normalisation (--norm spectral) keeps per-call generations on the host"
         if self.why_eager:
             print(f'deepliif_amd: StepGraph runs eagerly: {self.why_eager}')
         else:
@@ -641,7 +650,8 @@ class DeepLIIFModel(BaseModel):
         # 2N: sample by sample the same arithmetic as the reference's two calls (DeepLIIF_model.py:222-236), but every launch has twice the tiles -- the PatchGAN's
         # GEMM-shaped layers are the under-filled kernels of this step (64-128 tiles of 256 x 256 on 256 CUs at batch 8) -- and there are half as many launches.
         # BatchNorm discriminators keep the two calls (their statistics are per call).
-        paired = _D_PAIR_BATCH and all(getattr(getattr(self, 'net' + n), 'norm_kind', 'batch') != 'batch' for n in self.model_names_d)
+        # ... and so do spectrally normalised ones: one power iteration and one sigma per reference call (engine.SpectralSet)
+        paired = _D_PAIR_BATCH and all(_pairable(getattr(self, 'net' + n)) for n in self.model_names_d)
         real_mod_done = False
         for i, n in enumerate(self.model_names_d):
             with self._branch(i):
@@ -663,7 +673,7 @@ class DeepLIIFModel(BaseModel):
         real_mod_done = paired
         for n in self.model_names_ds:
             self._mark_net(tape, getattr(self, 'net' + n))
-        paired_seg = self.seg_gen and _D_PAIR_BATCH and all(getattr(getattr(self, 'net' + n), 'norm_kind', 'batch') != 'batch' for n in self.model_names_ds)
+        paired_seg = self.seg_gen and _D_PAIR_BATCH and all(_pairable(getattr(self, 'net' + n)) for n in self.model_names_ds)
         if paired_seg:
             # the five segmentation discriminators, each on cat(fake pairs, real pairs); weighted BEFORE the loss as in _seg_pred (:258-262)
             preds = []
@@ -919,7 +929,7 @@ class DeepLIIFExtModel(BaseModel):
         cg, cs, M = self.criterionGAN_mod, self.criterionGAN_seg, self.mod_gen_no
         rc = self._cat_real(ctx)                     # (main stream, before the fork)
         self._fork()                                 # (the gradients were zeroed on the main stream)
-        if _D_PAIR_BATCH and all(getattr(d, 'norm_kind', 'batch') != 'batch' for d in list(self.netD[:M]) + [d for d in self.netDS if d is not None]):
+        if _D_PAIR_BATCH and all(_pairable(d) for d in list(self.netD[:M]) + [d for d in self.netDS if d is not None]):
             # per-sample-normalised discriminators: the fake and the real inputs of each as ONE batch of 2N (see DeepLIIFModel.backward_D)
             def both_halves(parts_fake, parts_real):
                 nb, h, w, _ = parts_fake[0].t.shape

@@ -35,7 +35,8 @@ def get_norm_layer(norm_type='instance'):
         return functools.partial(nn.BatchNorm2d, affine=True, track_running_stats=True)
     if norm_type == 'instance':
         return functools.partial(nn.InstanceNorm2d, affine=False, track_running_stats=False)
-    if norm_type == 'none':
+    if norm_type in ('none', 'spectral'):
+        # networks.py:38: 'spectral' puts no norm LAYER anywhere (define_G / define_D wrap the conv weights instead, SpectralNorm below)
         return lambda c: Identity()
     raise NotImplementedError('normalization layer [%s] is not supported by the MI355X engine' % norm_type)
 
@@ -54,6 +55,34 @@ def _uses_bias(norm_layer) -> bool:
     return _norm_kind(norm_layer) == 'instance'
 
 
+def SpectralNorm(x, use_spectral_norm=False):
+    """networks.py:757-765: torch's own spectral_norm on the container module -- the reference's state_dict keys
+    (parametrizations.weight.original, parametrizations.weight.0._u / ._v), construction-time RNG draws and 15 warm-up iterations come with it.
+    The container's forward is never called: engine.SpectralSet runs the parametrization's arithmetic (csrc/spectral.hip)."""
+    if use_spectral_norm:
+        return nn.utils.parametrizations.spectral_norm(x)
+    return x
+
+
+def _conv_binding(spec: ConvSpec, m: nn.Module) -> E.ConvLayer:
+    """the engine layer of a Conv2d / ConvTranspose2d container, spectrally normalised or plain"""
+    if nn.utils.parametrize.is_parametrized(m, 'weight'):
+        plist = m.parametrizations.weight
+        return E.ConvLayer(spec, plist.original, m.bias, spectral_norm=plist[0])
+    return E.ConvLayer(spec, m.weight, m.bias)
+
+
+def _conv_layers_of(binding):
+    if isinstance(binding, E.ConvLayer):
+        yield binding
+    elif isinstance(binding, dict):
+        for v in binding.values():
+            yield from _conv_layers_of(v)
+    elif isinstance(binding, (list, tuple)):
+        for v in binding:
+            yield from _conv_layers_of(v)
+
+
 # -------------------------------------------------------------------------------------------------------------
 # engine-backed module base
 # -------------------------------------------------------------------------------------------------------------
@@ -65,6 +94,8 @@ class EngineNet(nn.Module):
         self.precision = DEFAULT_PRECISION
         self.batched_per_sample_norm = True     # N>1 inference reproduces N one-tile forwards
         self._bound = None
+        self.spectral_norm = False              # the conv weights are spectrally normalised (--norm spectral)
+        self._spectral = None                   # engine.SpectralSet over them, built with the bindings
 
     def set_precision(self, name: str):
         self.precision = name
@@ -73,12 +104,26 @@ class EngineNet(nn.Module):
     def _layers(self):
         if self._bound is None:
             self._bound = self._bind()
+            sn = [l for l in _conv_layers_of(self._bound) if l.sn is not None]
+            self._spectral = E.SpectralSet(sn) if sn else None
         return self._bound
+
+    def run(self, ctx: E.Ctx, x: E.Act) -> E.Act:
+        """one forward call of the network.  A spectrally normalised net first refreshes its SpectralSet: one power iteration in train() mode and this
+        call's effective weights / images (engine.SpectralSet.begin)"""
+        b = self._layers()
+        if self._spectral is None:
+            return self._run(b, ctx, x)
+        token = self._spectral.begin(ctx)
+        try:
+            return self._run(b, ctx, x)
+        finally:
+            self._spectral.end(token)
 
     def _bind(self):
         raise NotImplementedError
 
-    def run(self, ctx: E.Ctx, x: E.Act) -> E.Act:
+    def _run(self, b, ctx: E.Ctx, x: E.Act) -> E.Act:
         raise NotImplementedError
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
@@ -108,8 +153,6 @@ class ResnetBlock(nn.Module):
 
     def __init__(self, dim, padding_type, norm_layer, use_dropout, use_bias, use_spectral_norm=False):
         super().__init__()
-        if use_spectral_norm:
-            raise NotImplementedError('spectral norm is not on the MI355X hot path')
         if padding_type not in ('zero', 'reflect'):
             raise NotImplementedError('padding [%s] is not supported by the MI355X engine' % padding_type)
         seq: List[nn.Module] = []
@@ -118,7 +161,7 @@ class ResnetBlock(nn.Module):
             if padding_type == 'reflect':
                 seq.append(nn.ReflectionPad2d(1))
             self.idx[f'conv{half}'] = len(seq)
-            seq.append(nn.Conv2d(dim, dim, kernel_size=3, padding=1 if padding_type == 'zero' else 0, bias=use_bias))
+            seq.append(SpectralNorm(nn.Conv2d(dim, dim, kernel_size=3, padding=1 if padding_type == 'zero' else 0, bias=use_bias), use_spectral_norm))
             self.idx[f'norm{half}'] = len(seq)
             seq.append(norm_layer(dim))
             if half == 0:
@@ -134,32 +177,33 @@ class ResnetGenerator(EngineNet):
                  upsample='convtranspose', use_spectral_norm=False):
         assert n_blocks >= 0
         super().__init__()
-        if upsample not in ('convtranspose', 'resize_conv') or use_spectral_norm:
+        if upsample not in ('convtranspose', 'resize_conv'):
             # 'pixel_shuffle' cannot be constructed in the reference either (networks.py:416-420 passes kernel_size to SpectralNorm: TypeError)
-            raise NotImplementedError('upsample=convtranspose | resize_conv without spectral norm are on the MI355X hot path')
+            raise NotImplementedError('upsample=convtranspose | resize_conv are on the MI355X hot path')
         self.upsample = upsample
+        self.spectral_norm = sn = bool(use_spectral_norm)
         self.norm_kind = _norm_kind(norm_layer)
         self.padding_type = padding_type
         self.n_blocks = n_blocks
         self.ngf, self.input_nc, self.output_nc = ngf, input_nc, output_nc
         use_bias = _uses_bias(norm_layer)
         pad3 = nn.ReflectionPad2d(3) if padding_type == 'reflect' else nn.ZeroPad2d(3)
-        seq: List[nn.Module] = [pad3, nn.Conv2d(input_nc, ngf, kernel_size=7, padding=0, bias=use_bias), norm_layer(ngf), nn.ReLU(True)]
+        seq: List[nn.Module] = [pad3, SpectralNorm(nn.Conv2d(input_nc, ngf, kernel_size=7, padding=0, bias=use_bias), sn), norm_layer(ngf), nn.ReLU(True)]
         for i in range(2):
             m = 2 ** i
-            seq += [nn.Conv2d(ngf * m, ngf * m * 2, kernel_size=3, stride=2, padding=1, bias=use_bias), norm_layer(ngf * m * 2), nn.ReLU(True)]
+            seq += [SpectralNorm(nn.Conv2d(ngf * m, ngf * m * 2, kernel_size=3, stride=2, padding=1, bias=use_bias), sn), norm_layer(ngf * m * 2), nn.ReLU(True)]
         for _ in range(n_blocks):
-            seq.append(ResnetBlock(ngf * 4, padding_type, norm_layer, use_dropout, use_bias))
+            seq.append(ResnetBlock(ngf * 4, padding_type, norm_layer, use_dropout, use_bias, use_spectral_norm=sn))
         for i in range(2):
             m = 2 ** (2 - i)
             if upsample == 'resize_conv':       # networks.py:409-415: nearest x2, ReflectionPad2d(1), Conv2d(k3, default bias)
-                seq += [nn.Upsample(scale_factor=2, mode='nearest'), nn.ReflectionPad2d(1), nn.Conv2d(ngf * m, ngf * m // 2, kernel_size=3, stride=1, padding=0),
-                        norm_layer(ngf * m // 2), nn.ReLU(True)]
+                seq += [nn.Upsample(scale_factor=2, mode='nearest'), nn.ReflectionPad2d(1),
+                        SpectralNorm(nn.Conv2d(ngf * m, ngf * m // 2, kernel_size=3, stride=1, padding=0), sn), norm_layer(ngf * m // 2), nn.ReLU(True)]
                 continue
-            seq += [nn.ConvTranspose2d(ngf * m, ngf * m // 2, kernel_size=3, stride=2, padding=1, output_padding=1, bias=use_bias),
+            seq += [SpectralNorm(nn.ConvTranspose2d(ngf * m, ngf * m // 2, kernel_size=3, stride=2, padding=1, output_padding=1, bias=use_bias), sn),
                     norm_layer(ngf * m // 2), nn.ReLU(True)]
         seq.append(nn.ReflectionPad2d(3) if padding_type == 'reflect' else nn.ZeroPad2d(3))
-        seq.append(nn.Conv2d(ngf, output_nc, kernel_size=7, padding=0))
+        seq.append(SpectralNorm(nn.Conv2d(ngf, output_nc, kernel_size=7, padding=0), sn))
         seq.append(nn.Tanh())
         self.model = nn.Sequential(*seq)
 
@@ -168,12 +212,12 @@ class ResnetGenerator(EngineNet):
         pm = L.PAD_REFLECT if self.padding_type == 'reflect' else L.PAD_ZERO
         m = self.model
         b = {}
-        b['stem'] = (E.ConvLayer(ConvSpec('conv', self.input_nc, ngf, 7, 1, 3, pm), m[1].weight, m[1].bias), _norm_binding(k, ngf, m[2]))
+        b['stem'] = (_conv_binding(ConvSpec('conv', self.input_nc, ngf, 7, 1, 3, pm), m[1]), _norm_binding(k, ngf, m[2]))
         b['down'] = []
         idx = 4
         for i in range(2):
             c = ngf * 2 ** i
-            b['down'].append((E.ConvLayer(ConvSpec('conv', c, 2 * c, 3, 2, 1), m[idx].weight, m[idx].bias), _norm_binding(k, 2 * c, m[idx + 1])))
+            b['down'].append((_conv_binding(ConvSpec('conv', c, 2 * c, 3, 2, 1), m[idx]), _norm_binding(k, 2 * c, m[idx + 1])))
             idx += 3
         b['blocks'] = []
         for _ in range(self.n_blocks):
@@ -182,26 +226,23 @@ class ResnetGenerator(EngineNet):
             ent = []
             for half in (0, 1):
                 cm, nm = cb[blk.idx[f'conv{half}']], cb[blk.idx[f'norm{half}']]
-                ent.append((E.ConvLayer(ConvSpec('conv', ngf * 4, ngf * 4, 3, 1, 1, pm), cm.weight, cm.bias), _norm_binding(k, ngf * 4, nm)))
+                ent.append((_conv_binding(ConvSpec('conv', ngf * 4, ngf * 4, 3, 1, 1, pm), cm), _norm_binding(k, ngf * 4, nm)))
             b['blocks'].append((ent, blk))
             idx += 1
         b['up'] = []
         for i in range(2):
             c = ngf * 2 ** (2 - i)
             if self.upsample == 'resize_conv':
-                b['up'].append((E.ConvLayer(ConvSpec('conv', c, c // 2, 3, 1, 1, L.PAD_REFLECT), m[idx + 2].weight, m[idx + 2].bias),
-                                _norm_binding(k, c // 2, m[idx + 3])))
+                b['up'].append((_conv_binding(ConvSpec('conv', c, c // 2, 3, 1, 1, L.PAD_REFLECT), m[idx + 2]), _norm_binding(k, c // 2, m[idx + 3])))
                 idx += 5
                 continue
-            b['up'].append((E.ConvLayer(ConvSpec('convT', c, c // 2, 3, 2, 1, out_pad=1), m[idx].weight, m[idx].bias),
-                            _norm_binding(k, c // 2, m[idx + 1])))
+            b['up'].append((_conv_binding(ConvSpec('convT', c, c // 2, 3, 2, 1, out_pad=1), m[idx]), _norm_binding(k, c // 2, m[idx + 1])))
             idx += 3
         idx += 1
-        b['head'] = E.ConvLayer(ConvSpec('conv', ngf, self.output_nc, 7, 1, 3, pm), m[idx].weight, m[idx].bias)
+        b['head'] = _conv_binding(ConvSpec('conv', ngf, self.output_nc, 7, 1, 3, pm), m[idx])
         return b
 
-    def run(self, ctx: E.Ctx, x: E.Act) -> E.Act:
-        b = self._layers()
+    def _run(self, b, ctx: E.Ctx, x: E.Act) -> E.Act:
         # sole_reader: the next convolution is the only reader of these activations (engine.norm_act); the last down stage's output is also the first
         # block's residual, so it is not promised to anyone
         c, n = b['stem']
@@ -297,11 +338,10 @@ class UnetGenerator(EngineNet):
                                has_upnorm='upnorm' in blk.pos))
         return levels
 
-    def run(self, ctx: E.Ctx, x: E.Act) -> E.Act:
+    def _run(self, lv, ctx: E.Ctx, x: E.Act) -> E.Act:
         """networks.py:611-615.  The in-place LeakyReLU makes every skip carry lrelu(h); the up-path ReLU then
         sees relu(lrelu(h)) = relu(h), so the concat buffer stores the raw pre-activations [h_d | u_d] and the consumers
         apply the activation while staging (in_act), with no standalone activation pass."""
-        lv = self._layers()
         D = len(lv)
         dev, dt = x.t.device, ctx.prec.dtype
         n = x.t.shape[0]
@@ -474,9 +514,8 @@ class AttU_Net(EngineNet):
                                psi=(conv_of(a.psi, ConvSpec('conv', a.F_int, 1, 1, 1, 0)), bn_of(a.psi, 1)))
         return dict(downs=downs, ups=ups, atts=atts)
 
-    def run(self, ctx: E.Ctx, x: E.Act) -> E.Act:
+    def _run(self, b, ctx: E.Ctx, x: E.Act) -> E.Act:
         """att_unet.py:153-199."""
-        b = self._layers()
         assert x.t.shape[1] % 256 == 0 and x.t.shape[2] % 256 == 0, 'AttU_Net halves the image eight times: H and W must be multiples of 256'
         xs = []
         h = x
@@ -513,37 +552,35 @@ class AttU_Net(EngineNet):
 class NLayerDiscriminator(EngineNet):
     def __init__(self, input_nc, ndf=64, n_layers=3, norm_layer=nn.BatchNorm2d, use_spectral_norm=False):
         super().__init__()
-        if use_spectral_norm:
-            raise NotImplementedError('spectral norm is not on the MI355X hot path')
         self.norm_kind = _norm_kind(norm_layer)
         use_bias = _uses_bias(norm_layer)
+        self.spectral_norm = sn = bool(use_spectral_norm)
         self.input_nc, self.ndf, self.n_layers = input_nc, ndf, n_layers
-        seq: List[nn.Module] = [nn.Conv2d(input_nc, ndf, kernel_size=4, stride=2, padding=1), nn.LeakyReLU(0.2, True)]
+        seq: List[nn.Module] = [SpectralNorm(nn.Conv2d(input_nc, ndf, kernel_size=4, stride=2, padding=1), sn), nn.LeakyReLU(0.2, True)]
         prev = 1
         self._chan = []
         for n in range(1, n_layers + 1):
             mult = min(2 ** n, 8)
             stride = 2 if n < n_layers else 1
-            seq += [nn.Conv2d(ndf * prev, ndf * mult, kernel_size=4, stride=stride, padding=1, bias=use_bias), norm_layer(ndf * mult),
+            seq += [SpectralNorm(nn.Conv2d(ndf * prev, ndf * mult, kernel_size=4, stride=stride, padding=1, bias=use_bias), sn), norm_layer(ndf * mult),
                     nn.LeakyReLU(0.2, True)]
             self._chan.append((ndf * prev, ndf * mult, stride))
             prev = mult
-        seq.append(nn.Conv2d(ndf * prev, 1, kernel_size=4, stride=1, padding=1))
+        seq.append(SpectralNorm(nn.Conv2d(ndf * prev, 1, kernel_size=4, stride=1, padding=1), sn))
         self._last_in = ndf * prev
         self.model = nn.Sequential(*seq)
 
     def _bind(self):
         m, k = self.model, self.norm_kind
-        b = {'first': E.ConvLayer(ConvSpec('conv', self.input_nc, self.ndf, 4, 2, 1), m[0].weight, m[0].bias), 'mid': []}
+        b = {'first': _conv_binding(ConvSpec('conv', self.input_nc, self.ndf, 4, 2, 1), m[0]), 'mid': []}
         idx = 2
         for cin, cout, stride in self._chan:
-            b['mid'].append((E.ConvLayer(ConvSpec('conv', cin, cout, 4, stride, 1), m[idx].weight, m[idx].bias), _norm_binding(k, cout, m[idx + 1])))
+            b['mid'].append((_conv_binding(ConvSpec('conv', cin, cout, 4, stride, 1), m[idx]), _norm_binding(k, cout, m[idx + 1])))
             idx += 3
-        b['last'] = E.ConvLayer(ConvSpec('conv', self._last_in, 1, 4, 1, 1), m[idx].weight, m[idx].bias)
+        b['last'] = _conv_binding(ConvSpec('conv', self._last_in, 1, 4, 1, 1), m[idx])
         return b
 
-    def run(self, ctx: E.Ctx, x: E.Act) -> E.Act:
-        b = self._layers()
+    def _run(self, b, ctx: E.Ctx, x: E.Act) -> E.Act:
         h = E.conv(ctx, x, b['first'], act=L.ACT_LRELU)
         for i, (c, n) in enumerate(b['mid']):
             nxt = b['mid'][i + 1][0] if i + 1 < len(b['mid']) else b['last']          # the only reader of this activation
@@ -575,8 +612,7 @@ class PixelDiscriminator(EngineNet):
                 'c1': (E.ConvLayer(ConvSpec('conv', self.ndf, self.ndf * 2, 1, 1, 0), m[2].weight, m[2].bias), _norm_binding(self.norm_kind, self.ndf * 2, m[3])),
                 'c2': E.ConvLayer(ConvSpec('conv', self.ndf * 2, 1, 1, 1, 0), m[5].weight, m[5].bias)}
 
-    def run(self, ctx: E.Ctx, x: E.Act) -> E.Act:
-        b = self._layers()
+    def _run(self, b, ctx: E.Ctx, x: E.Act) -> E.Act:
         h = E.conv(ctx, x, b['c0'], act=L.ACT_LRELU)
         c, n = b['c1']
         h = E.norm_act(ctx, E.conv(ctx, h, c, stats=n is not None), n, L.ACT_LRELU)
@@ -627,10 +663,11 @@ def init_net(net, init_type='normal', init_gain=0.02, gpu_ids=[]):
 def define_G(input_nc, output_nc, ngf, netG, norm='batch', use_dropout=False, init_type='normal', init_gain=0.02, gpu_ids=[],
              padding_type='reflect', upsample='convtranspose'):
     norm_layer = get_norm_layer(norm_type=norm)
+    use_spectral_norm = norm == 'spectral'          # networks.py:173-178: forwarded to ResnetGenerator only (the UNets stay plain)
     if netG.startswith('resnet_'):
         n_blocks = int(netG.split('_')[1].replace('blocks', ''))
         net = ResnetGenerator(input_nc, output_nc, ngf, norm_layer=norm_layer, use_dropout=use_dropout, n_blocks=n_blocks,
-                              padding_type=padding_type, upsample=upsample)
+                              padding_type=padding_type, upsample=upsample, use_spectral_norm=use_spectral_norm)
     elif netG in ('unet_32', 'unet_64', 'unet_128', 'unet_256', 'unet_512'):
         downs = {'unet_32': 5, 'unet_64': 6, 'unet_128': 7, 'unet_256': 8, 'unet_512': 9}[netG]
         net = UnetGenerator(input_nc, output_nc, downs, ngf, norm_layer=norm_layer, use_dropout=use_dropout)
@@ -643,10 +680,11 @@ def define_G(input_nc, output_nc, ngf, netG, norm='batch', use_dropout=False, in
 
 def define_D(input_nc, ndf, netD, n_layers_D=3, norm='batch', init_type='normal', init_gain=0.02, gpu_ids=[]):
     norm_layer = get_norm_layer(norm_type=norm)
+    use_spectral_norm = norm == 'spectral'          # networks.py:228-233: NLayerDiscriminator only (PixelDiscriminator stays plain)
     if netD == 'basic':
-        net = NLayerDiscriminator(input_nc, ndf, n_layers=3, norm_layer=norm_layer)
+        net = NLayerDiscriminator(input_nc, ndf, n_layers=3, norm_layer=norm_layer, use_spectral_norm=use_spectral_norm)
     elif netD == 'n_layers':
-        net = NLayerDiscriminator(input_nc, ndf, n_layers_D, norm_layer=norm_layer)
+        net = NLayerDiscriminator(input_nc, ndf, n_layers_D, norm_layer=norm_layer, use_spectral_norm=use_spectral_norm)
     elif netD == 'pixel':
         net = PixelDiscriminator(input_nc, ndf, norm_layer=norm_layer)
     else:
@@ -698,10 +736,10 @@ class Vgg19(EngineNet):
                 prog.append((i, None))
         return prog
 
-    def run(self, ctx: E.Ctx, x: E.Act):
+    def _run(self, prog, ctx: E.Ctx, x: E.Act):
         """-> [h_relu1 .. h_relu5] (networks.py:722-731)"""
         outs, h = [], x
-        for i, layer in self._layers():
+        for i, layer in prog:
             h = E.maxpool2(ctx, h) if layer is None else E.conv(ctx, h, layer, act=L.ACT_RELU)
             if i + 2 in VGG19_SLICE_ENDS:            # the ReLU that closes a slice sits right after this conv
                 outs.append(h)

@@ -164,6 +164,28 @@ class PackedWeights:
         self.lo = torch.empty(n, dtype=torch.int16, device=device) if with_lo else None
 
 
+class SpectralJob:
+    """One spectrally normalised conv weight of one forward call (HipBackend.spectral_table): w the master weight
+    (parametrizations.weight.original), dim the _SpectralNorm's matrix dimension (0: Conv2d, 1: ConvTranspose2d), u / v the module's
+    buffers, weff / u_snap / v_snap / sigma what the call leaves behind, g / grad the two gradients (both None: the job never runs backward)."""
+    __slots__ = ('w', 'dim', 'u', 'v', 'weff', 'u_snap', 'v_snap', 'sigma', 'g', 'grad')
+
+    def __init__(self, w, dim, u, v, weff, u_snap, v_snap, sigma, g=None, grad=None):
+        self.w, self.dim, self.u, self.v, self.weff, self.u_snap, self.v_snap, self.sigma, self.g, self.grad = w, dim, u, v, weff, u_snap, v_snap, sigma, g, grad
+
+    def matrix_shape(self):
+        """(rows, columns, KH * KW) of the matrix view"""
+        rows = self.w.shape[self.dim]
+        return rows, self.w.numel() // rows, self.w.shape[2] * self.w.shape[3]
+
+    def pointers(self):
+        return tuple(0 if t is None else t.data_ptr() for t in (self.w, self.u, self.v, self.weff, self.u_snap, self.v_snap, self.sigma, self.g, self.grad))
+
+
+class SpectralTable:
+    """device-resident job records and workgroup tables of one set of SpectralJobs"""
+
+
 def _ptr(t: Optional[torch.Tensor]):
     return None if t is None else C.c_void_p(t.data_ptr())
 
@@ -277,6 +299,63 @@ class HipBackend:
         jobs_dev, tab_dev, nblocks = table
         _need_cuda(jobs_dev, tab_dev)
         self.check(self.lib.dl_pack_weights_batch(_ptr(jobs_dev), _ptr(tab_dev), nblocks, _stream()), 'dl_pack_weights_batch')
+
+    # ---- spectral normalisation of conv weights (csrc/spectral.hip; engine.SpectralSet owns the tensors)
+    def spectral_table(self, jobs):
+        """jobs: [SpectralJob] -> SpectralTable: the device-resident job records + workgroup tables of dl_spectral_forward / _backward (built once per set
+        of pointers; nothing is launched)"""
+        lib = self.lib
+        jb = int(lib.dl_spectral_job_bytes())
+        host = (C.c_ubyte * (jb * len(jobs)))()
+        base = C.addressof(host)
+        off = 0
+        for i, j in enumerate(jobs):
+            _need_cuda(j.w, j.u, j.v, j.weff, j.u_snap, j.v_snap, j.sigma, j.g, j.grad)
+            for t in (j.w, j.weff, j.g, j.grad):
+                assert t is None or (t.dtype == torch.float32 and t.is_contiguous() and t.shape == j.w.shape)
+            rows, cols, kk = j.matrix_shape()
+            assert j.u.numel() == rows and j.v.numel() == cols and j.u_snap.numel() == rows and j.v_snap.numel() == cols
+            self.check(lib.dl_spectral_job_fill(_ptr(j.w), rows, cols, kk, j.dim, _ptr(j.u), _ptr(j.v), _ptr(j.weff), _ptr(j.u_snap), _ptr(j.v_snap),
+                                                _ptr(j.sigma), _ptr(j.g), _ptr(j.grad), off, C.c_void_p(base + i * jb)), 'dl_spectral_job_fill')
+            off += int(lib.dl_spectral_scratch_floats(rows, cols))
+        dev = jobs[0].w.device
+        tabs = []
+        for kind in range(3):
+            n = int(lib.dl_spectral_blocks(C.c_void_p(base), len(jobs), kind, None))
+            if n < 0:
+                self.check(n, 'dl_spectral_blocks')
+            tab = (C.c_int32 * (2 * max(n, 1)))()
+            self.check(min(int(lib.dl_spectral_blocks(C.c_void_p(base), len(jobs), kind, C.c_void_p(C.addressof(tab)))), 0), 'dl_spectral_blocks')
+            tabs.append((torch.frombuffer(tab, dtype=torch.int32).clone()[:2 * n], n))
+        t = SpectralTable()
+        t.count, t.scratch_floats, t.device = len(jobs), off, dev
+        t.jobs_dev = torch.frombuffer(host, dtype=torch.uint8).clone().to(dev)
+        t.tiles_host = tabs[0][0].view(-1, 2)
+        t.tiles, t.rows, t.cols = [(tab.to(dev), n) for tab, n in tabs]
+        t.subsets = {}
+        return t
+
+    def spectral_forward(self, table: 'SpectralTable', iterate: bool):
+        _LAUNCH.dev = table.device
+        ws = WS.get('spectral', table.scratch_floats, table.device)
+        self.check(self.lib.dl_spectral_forward(_ptr(table.jobs_dev), table.count, _ptr(table.tiles[0]), table.tiles[1], _ptr(table.rows[0]), table.rows[1],
+                                                _ptr(table.cols[0]), table.cols[1], _ptr(ws), 1 if iterate else 0, _stream()), 'dl_spectral_forward')
+
+    def spectral_backward(self, table: 'SpectralTable', accumulate: bool, only=None):
+        """only: tuple of job indices (the trainable layers) or None for every job of the table"""
+        tiles = table.tiles
+        if only is not None and len(only) != table.count:
+            tiles = table.subsets.get(only)
+            if tiles is None:
+                keep = torch.isin(table.tiles_host[:, 0], torch.tensor(list(only), dtype=torch.int32))
+                sub = table.tiles_host[keep].contiguous()
+                tiles = table.subsets[only] = (sub.view(-1).to(table.device), int(sub.shape[0]))
+        if tiles[1] == 0:
+            return
+        _LAUNCH.dev = table.device
+        ws = WS.get('spectral', table.scratch_floats, table.device)
+        self.check(self.lib.dl_spectral_backward(_ptr(table.jobs_dev), table.count, _ptr(tiles[0]), tiles[1], _ptr(ws), 1 if accumulate else 0, _stream()),
+                   'dl_spectral_backward')
 
     # ---- convolution forward / data-gradient (gather GEMM)
     def conv_forward(self, packed: PackedWeights, x: torch.Tensor, out: torch.Tensor, hq: int, wq: int, bias: Optional[torch.Tensor],

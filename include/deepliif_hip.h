@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define DL_VERSION 114
+#define DL_VERSION 115
 
 enum { DL_F32 = 0, DL_BF16 = 1 };           /* DL_BF16 = "the 16-bit type of this library": bfloat16, or IEEE half in libdeepliif_hip_f16.so (below) */
 enum { DL_HALF_BF16 = 0, DL_HALF_FP16 = 1 };   /* dl_half_format() */
@@ -253,6 +253,29 @@ size_t dl_pack_job_bytes(void);
 int dl_pack_job_fill(const dl_pack_desc *d, const float *src, void *w_hi, void *w_lo, void *job_host);
 int dl_pack_batch_blocks(const void *jobs_host, int count, int32_t *block_tab_host);
 int dl_pack_weights_batch(const void *jobs_dev, const int32_t *block_tab_dev, int nblocks, void *stream);
+
+/* Spectral normalisation of conv weights (`--norm spectral`: networks.py:38,173,228,757-765 of the reference wrap every Conv2d / ConvTranspose2d of
+ * ResnetGenerator and NLayerDiscriminator in torch.nn.utils.parametrizations.spectral_norm).  Per layer, with M the [Cout] x [Cin*KH*KW] matrix view of
+ * the weight W (dim 0: Conv2d, M = W.flatten(1); dim 1: ConvTranspose2d, M = W.permute(1,0,2,3).flatten(1), read in place -- no permuted copy):
+ *   forward : when iterating, u <- normalize(M v), v <- normalize(M^T u)  (eps 1e-12, in place on _u / _v); in either mode
+ *             sigma = u^T (M v), weff = W / sigma (W's shape and layout), and u, v, sigma of THIS call are left in u_snap / v_snap / sigma
+ *   backward: grad (+)= (g - <g, weff> u_snap v_snap^T) / sigma, g the gradient w.r.t. weff (u, v are constants of the graph)
+ * fp32 whatever the precision policy.  The layers of a network are batched like dl_pack_weights_batch: dl_spectral_job_fill() writes an opaque record of
+ * dl_spectral_job_bytes() bytes into HOST memory (pointers are only recorded, nothing is launched; g / grad may both be NULL for a job that never runs
+ * backward), dl_spectral_blocks() turns `count` back-to-back records into a workgroup table of int32 pairs {job, index} -- kind 0: one entry per
+ * 16-row x 1024-column tile, 1: per row tile, 2: per column tile; NULL returns the entry count -- and the caller copies records and tables to the device once.
+ * `scratch_off` is the job's region (dl_spectral_scratch_floats(rows, cols) floats, a multiple of 4) of the caller's scratch buffer.
+ * dl_spectral_forward launches 7 kernels (3 when not iterating) and dl_spectral_backward 2, whatever `count`; a layer spreads over as many workgroups as
+ * it has tiles.  Cross-workgroup sums go through per-tile partials in the scratch that the next launch adds in index order: no atomics, two runs give the
+ * same bits; nothing is read back to the host.  dl_spectral_backward may be given the tile table of a SUBSET of the jobs (the trainable layers). */
+size_t dl_spectral_job_bytes(void);
+size_t dl_spectral_scratch_floats(int rows, int cols);
+int dl_spectral_job_fill(const float *w, int rows, int cols, int kk, int dim, float *u, float *v, float *weff, float *u_snap, float *v_snap, float *sigma,
+                         const float *g, float *grad, int64_t scratch_off, void *job_host);
+int dl_spectral_blocks(const void *jobs_host, int count, int kind, int32_t *tab_host);
+int dl_spectral_forward(const void *jobs_dev, int count, const int32_t *tiles_dev, int ntiles, const int32_t *rows_dev, int nrows, const int32_t *cols_dev,
+                        int ncols, float *scratch, int do_power_iteration, void *stream);
+int dl_spectral_backward(const void *jobs_dev, int count, const int32_t *tiles_dev, int ntiles, float *scratch, int accumulate, void *stream);
 
 /* Narrow-Cout convolutions (the 7x7 ResnetGenerator head, networks.py:438-443: 64 -> 3 channels): an MFMA tile has at least 16
  * output rows, so Cout = 3 would waste 13/16 of the matrix pipe.  The kernel column is folded into the GEMM rows instead:
