@@ -16,7 +16,7 @@ import contextlib
 import os
 import sys
 from collections import OrderedDict
-from typing import List, Optional
+from typing import List, NamedTuple, Optional
 
 import torch
 
@@ -77,7 +77,7 @@ def pick_gpu(gpu_ids, is_train: bool, env=None) -> int:
                               'then takes gpu_ids[LOCAL_RANK] and the gradients are averaged over RCCL, deepliif_amd.distributed)')
 
 
-# A/B switch (DL_D_PAIR_BATCH=0): the discriminators see the fake pairs and the real pairs in two calls, as in rounds 1-5 (DeepLIIFModel.backward_D)
+# A/B switch (DL_D_PAIR_BATCH=0): the discriminators see the fake pairs and the real pairs in two calls, as in rounds 1-5 (BaseModel._discriminator_pass)
 _D_PAIR_BATCH = os.environ.get('DL_D_PAIR_BATCH', '1') != '0'
 
 
@@ -85,6 +85,19 @@ def _pairable(d) -> bool:
     """may a discriminator see the fake pairs and the real pairs as ONE batch?  Only if every sample is normalised on its own (no BatchNorm) and its weights
     are the same for both calls (not spectrally normalised: the reference's two calls run two power iterations and divide by two sigmas)"""
     return getattr(d, 'norm_kind', 'batch') != 'batch' and not getattr(d, 'spectral_norm', False)
+
+
+class DJob(NamedTuple):
+    """one (fake, real) pair of loss terms of a discriminator pass (BaseModel._discriminator_pass)"""
+    branch: Optional[int]                   # index of the branch stream the job runs on; None: the main stream
+    nets: list                              # the discriminator, or several whose predictions are summed with `sum_weights` BEFORE the loss (DeepLIIF_model.py:258-262)
+    fake: list                              # per net: the parts (E.Act) of its fake input, for concat_channels; generated images come detached
+    real: list                              # per net: the parts of its real input
+    crit: object                            # networks.GANLoss
+    weight: float
+    slots: tuple                            # (fake, real) loss slots
+    paired: bool                            # the nets see cat(fake, real) as ONE batch of 2N (_pairable)
+    sum_weights: Optional[list] = None
 
 
 class StepGraph:
@@ -337,9 +350,9 @@ class BaseModel:
                 tape.record(self._fork)
 
     def _branch(self, i):
-        """context: the kernels launched (and the tensors allocated) inside belong to the stream of branch i"""
+        """context: the kernels launched (and the tensors allocated) inside belong to the stream of branch i (None: stay on the current, the main, stream)"""
         streams = self._branch_streams()
-        return torch.cuda.stream(streams[i % len(streams)]) if streams else contextlib.nullcontext()
+        return torch.cuda.stream(streams[i % len(streams)]) if (streams and i is not None) else contextlib.nullcontext()
 
     def _new_tape(self):
         return E.Tape(streams=self._branch_streams() is not None)
@@ -357,6 +370,109 @@ class BaseModel:
 
     def _net_gpu_ids(self):
         return self.gpu_ids
+
+    # ---- what the training step of every model class is made of --------------------------------------------------------------------------------
+    def _ctx(self, tape, training=True):
+        return E.Ctx(self.precision, self._hook_tape(tape), training=training)
+
+    def _slot(self, name):
+        """where a loss kernel writes loss_<name>: a 1-element view into the loss buffer"""
+        return self._loss_buf[self._loss_index[name]].view(1)
+
+    def _make_optimizers(self, params_g, params_d, opt):
+        OptCls = networks.get_optimizer(_get(opt, 'optimizer', 'adam'))
+        try:
+            self.optimizer_G = OptCls(params_g, lr=opt.lr_g, betas=(opt.beta1, 0.999))
+            self.optimizer_D = OptCls(params_d, lr=opt.lr_d, betas=(opt.beta1, 0.999))
+        except TypeError:
+            self.optimizer_G = OptCls(params_g, lr=opt.lr_g)
+            self.optimizer_D = OptCls(params_d, lr=opt.lr_d)
+        self.optimizers += [self.optimizer_G, self.optimizer_D]
+
+    def _scale_reported(self, key, factor):
+        """after backward: the loss slots with `key` in their name are reported multiplied by `factor`, as the reference logs them (loss_G_L1 * lambda_L1,
+        DeepLIIF_model.py:398-400); factor None: the term was not evaluated and reads NaN, not a plausible-looking 0.0.  The index tensor is built ONCE:
+        torch.tensor(..., device=cuda) is a host-to-device copy per step (and not capturable, models.StepGraph)."""
+        cache = self.__dict__.setdefault('_slots_with', {})
+        if key not in cache:
+            cache[key] = torch.tensor([self._loss_index[n] for n in self.loss_names if key in n], dtype=torch.long, device=self.device)
+        sel = cache[key]
+        if not sel.numel():
+            return
+        if factor is None:
+            self._loss_buf[sel] = float('nan')
+        else:
+            self._loss_buf[sel] *= factor
+
+    def _discriminator_pass(self, tape, ctx, jobs: List[DJob], cached_real=None):
+        """The forward half of backward_D (DeepLIIF_model.py:205-332): every job's discriminators on their fake and on their real inputs, two loss terms per job.
+        A discriminator that normalises every sample on its own statistics (InstanceNorm, or no norm layer) sees the fake and the real inputs as ONE batch of 2N
+        (job.paired): sample by sample the same arithmetic as the reference's two calls (:222-236), but every launch has twice the tiles -- the PatchGAN's
+        GEMM-shaped layers are the under-filled kernels of this step (64-128 tiles of 256 x 256 on 256 CUs at batch 8) -- and there are half as many launches.
+        BatchNorm discriminators keep the two calls (their statistics are per call), and so do spectrally normalised ones (one power iteration and one sigma per
+        reference call, engine.SpectralSet): for those, ALL fake passes are issued before ALL real passes, per network fake then real.
+        cached_real: callable giving, per job, the ready real inputs of its nets instead of job.real; asked once, between the two phases, outside the branches."""
+        def both_halves(fake, real):
+            nb, h, w, _ = fake[0].t.shape
+            c = sum(p.C for p in fake)
+            both = torch.zeros((2 * nb, h, w, E.cpad(c)), dtype=fake[0].t.dtype, device=fake[0].t.device)
+            E.concat_channels(ctx, fake, out=both[:nb])
+            E.concat_channels(ctx, real, out=both[nb:])
+            return E.Act(both, c)
+
+        def predict(job, net_input):
+            preds = [net.run(ctx, net_input(k)) for k, net in enumerate(job.nets)]
+            return preds[0] if job.sum_weights is None else E.weighted_sum(ctx, preds, job.sum_weights)
+
+        for job in jobs:
+            c = job.crit
+            with self._branch(job.branch):
+                # a two-call discriminator runs twice (fake, real): mark before the first use -- on the stream of its branch: the marker's all-reduce is
+                # ordered behind THAT stream
+                for net in job.nets:
+                    self._mark_net(tape, net)
+                if job.paired:
+                    pred = predict(job, lambda k: both_halves(job.fake[k], job.real[k]))
+                    E.loss_op_halves(ctx, c.kind, pred, (c.target(False), c.target(True)), job.weight, job.slots)
+                else:
+                    pred = predict(job, lambda k: E.concat_channels(ctx, job.fake[k]))
+                    E.loss_op(ctx, c.kind, pred, None, c.target(False), job.weight, job.slots[0])
+        two_calls = [(j, job) for j, job in enumerate(jobs) if not job.paired]
+        ready = cached_real() if (cached_real is not None and two_calls) else None
+        for j, job in two_calls:
+            c = job.crit
+            with self._branch(job.branch):
+                pred = predict(job, (lambda k: ready[j][k]) if ready is not None else (lambda k: E.concat_channels(ctx, job.real[k])))
+                E.loss_op(ctx, c.kind, pred, None, c.target(True), job.weight, job.slots[1])
+
+    def _update(self, optimizer, *backward):
+        """one optimizer's share of a step: zero its gradients, run the backward pass(es) inside its gradient exchange (a network's slice goes on the wire as
+        soon as its backward is done), step"""
+        optimizer.zero_grad()
+        self.exchange.begin(optimizer)
+        for run in backward:
+            run()
+        self.exchange.finish(optimizer)
+        optimizer.step()
+
+    def optimize_parameters(self):
+        """DeepLIIF_model.py:431-467."""
+        self._sync_replicas()
+        self.forward()
+        self.set_requires_grad(self._d_nets(), True)
+        self._update(self.optimizer_D, self.backward_D)      # its exchange cannot hide: D must be updated before backward_G runs it
+        self.set_requires_grad(self._d_nets(), False)
+        self._update(self.optimizer_G, self.backward_G)
+
+    def calculate_losses(self):
+        """DeepLIIF_model.py:469-507: losses + gradients without the optimizer steps (validation)."""
+        self.forward()
+        self.set_requires_grad(self._d_nets(), True)
+        self.optimizer_D.zero_grad()
+        self.backward_D()
+        self.set_requires_grad(self._d_nets(), False)
+        self.optimizer_G.zero_grad()
+        self.backward_G()
 
     # -- lifecycle -------------------------------------------------------------------------------------------
     def setup(self, opt):
@@ -544,14 +660,7 @@ class DeepLIIFModel(BaseModel):
             self.branch_parallel = type(self) is DeepLIIFModel and self.criterionVGG is None and (not self.seg_gen or _SEG_STREAMS)
             params_g = [p for n in self.model_names_g + self.model_names_gs for p in getattr(self, 'net' + n).parameters()]
             params_d = [p for n in self.model_names_d + self.model_names_ds for p in getattr(self, 'net' + n).parameters()]
-            OptCls = networks.get_optimizer(_get(opt, 'optimizer', 'adam'))
-            try:
-                self.optimizer_G = OptCls(params_g, lr=opt.lr_g, betas=(opt.beta1, 0.999))
-                self.optimizer_D = OptCls(params_d, lr=opt.lr_d, betas=(opt.beta1, 0.999))
-            except TypeError:
-                self.optimizer_G = OptCls(params_g, lr=opt.lr_g)
-                self.optimizer_D = OptCls(params_d, lr=opt.lr_d)
-            self.optimizers += [self.optimizer_G, self.optimizer_D]
+            self._make_optimizers(params_g, params_d, opt)
             self.exchange = GradExchanger()
             self._vgg_buf = torch.zeros(max(M, 1), dtype=torch.float32, device=self.device)
         self._tape_G: Optional[E.Tape] = None
@@ -576,9 +685,6 @@ class DeepLIIFModel(BaseModel):
         self._B = [E.to_engine(getattr(self, f'real_B_{i + 1}'), p) for i in range(M)]
         self._Bseg = E.to_engine(getattr(self, f'real_B_{S}'), p) if self.seg_gen else None
         self._real_pairs = None
-
-    def _ctx(self, tape, training=True):
-        return E.Ctx(self.precision, self._hook_tape(tape), training=training)
 
     def forward(self, record: Optional[bool] = None):
         """DeepLIIF_model.py:175-203."""
@@ -616,18 +722,15 @@ class DeepLIIFModel(BaseModel):
 
     # ---------------------------------------------------------------------------------------------------------
     def _pairs_real(self, ctx):
+        """the real pairs of the two-call route, per job of backward_D: [[cat(A, B_i)] for D_i] + [[cat(cond_k, B_seg) for DS_k]]; made once per batch"""
         if self._real_pairs is None:
-            M = self.opt.modalities_no
-            mod = []
-            for i in range(M):
+            pairs = []
+            for i, b in enumerate(self._B):
                 with self._branch(i):
-                    mod.append(E.concat_channels(ctx, [self._A, self._B[i]]))
-            seg = []
+                    pairs.append([E.concat_channels(ctx, [self._A, b])])
             if self.seg_gen:
-                for i in range(M + 1):
-                    cond = self._A if i == 0 else self._B[i - 1]
-                    seg.append(E.concat_channels(ctx, [cond, self._Bseg]))
-            self._real_pairs = (mod, seg)
+                pairs.append([E.concat_channels(ctx, [cond, self._Bseg]) for cond in [self._A] + self._B])
+            self._real_pairs = pairs
         return self._real_pairs
 
     def _seg_pred(self, ctx, image: E.Act):
@@ -639,68 +742,22 @@ class DeepLIIFModel(BaseModel):
         return E.weighted_sum(ctx, preds, self.seg_weights[:M + 1])   # weighted BEFORE the lsgan loss (:258-262)
 
     def backward_D(self):
-        """DeepLIIF_model.py:205-332: D losses on detached fakes and on real pairs."""
+        """DeepLIIF_model.py:205-332: D losses on detached fakes and on real pairs.  Each family decides on its own whether it sees them as one batch."""
         tape = self._new_tape()
         ctx = self._ctx(tape)
         M, S = self.opt.modalities_no, self.mod_id_seg
         wD = self.loss_D_weights
-        cg, cs = self.criterionGAN_mod, self.criterionGAN_seg
+        nets_d, nets_ds = ([getattr(self, 'net' + n) for n in names] for names in (self.model_names_d, self.model_names_ds))
+        paired, paired_seg = (_D_PAIR_BATCH and all(_pairable(d) for d in nets) for nets in (nets_d, nets_ds))
+        jobs = [DJob(i, [d], [[self._A, self._fake[i].detach()]], [[self._A, self._B[i]]], self.criterionGAN_mod, 0.5 * wD[i],
+                     (self._slot(f'D_fake_{i + 1}'), self._slot(f'D_real_{i + 1}')), paired=paired) for i, d in enumerate(nets_d)]
+        if self.seg_gen:
+            # the seg discriminators read the summed seg image: main stream; conditioned on the real modalities and weighted BEFORE the loss, as in _seg_pred
+            conds, fake_seg = [self._A] + self._B, self._fake_seg.detach()
+            jobs.append(DJob(None, nets_ds, [[c, fake_seg] for c in conds], [[c, self._Bseg] for c in conds], self.criterionGAN_seg, 0.5 * wD[M],
+                             (self._slot(f'D_fake_{S}'), self._slot(f'D_real_{S}')), paired=paired_seg, sum_weights=self.seg_weights[:M + 1]))
         self._fork()                             # (the gradients were zeroed on the main stream)
-        # A discriminator that normalises every sample on its own statistics (InstanceNorm, or no norm layer) sees the fake pairs and the real pairs as ONE batch of
-        # 2N: sample by sample the same arithmetic as the reference's two calls (DeepLIIF_model.py:222-236), but every launch has twice the tiles -- the PatchGAN's
-        # GEMM-shaped layers are the under-filled kernels of this step (64-128 tiles of 256 x 256 on 256 CUs at batch 8) -- and there are half as many launches.
-        # BatchNorm discriminators keep the two calls (their statistics are per call).
-        # ... and so do spectrally normalised ones: one power iteration and one sigma per reference call (engine.SpectralSet)
-        paired = _D_PAIR_BATCH and all(_pairable(getattr(self, 'net' + n)) for n in self.model_names_d)
-        real_mod_done = False
-        for i, n in enumerate(self.model_names_d):
-            with self._branch(i):
-                # every discriminator runs twice below (fake, real): mark before the first use -- on the stream of its branch: the marker's all-reduce is
-                # ordered behind THAT stream
-                self._mark_net(tape, getattr(self, 'net' + n))
-                if paired:
-                    nb, h, w, _ = self._A.t.shape
-                    both = torch.zeros((2 * nb, h, w, E.cpad(self._A.C + self._fake[i].C)), dtype=self._A.t.dtype, device=self._A.t.device)
-                    E.concat_channels(ctx, [self._A, self._fake[i].detach()], out=both[:nb])
-                    E.concat_channels(ctx, [self._A, self._B[i]], out=both[nb:])
-                    pred = getattr(self, 'net' + n).run(ctx, E.Act(both, self._A.C + self._fake[i].C))
-                    E.loss_op_halves(ctx, cg.kind, pred, (cg.target(False), cg.target(True)), 0.5 * wD[i],
-                                     (getattr(self, f'loss_D_fake_{i + 1}').view(1), getattr(self, f'loss_D_real_{i + 1}').view(1)))
-                    continue
-                pair = E.concat_channels(ctx, [self._A, self._fake[i].detach()])
-                pred = getattr(self, 'net' + n).run(ctx, pair)
-                E.loss_op(ctx, cg.kind, pred, None, cg.target(False), 0.5 * wD[i], getattr(self, f'loss_D_fake_{i + 1}').view(1))
-        real_mod_done = paired
-        for n in self.model_names_ds:
-            self._mark_net(tape, getattr(self, 'net' + n))
-        paired_seg = self.seg_gen and _D_PAIR_BATCH and all(_pairable(getattr(self, 'net' + n)) for n in self.model_names_ds)
-        if paired_seg:
-            # the five segmentation discriminators, each on cat(fake pairs, real pairs); weighted BEFORE the loss as in _seg_pred (:258-262)
-            preds = []
-            nb, h, w, _ = self._A.t.shape
-            for i, n in enumerate(self.model_names_ds):
-                cond = self._A if i == 0 else self._B[i - 1]
-                both = torch.zeros((2 * nb, h, w, E.cpad(cond.C + self._fake_seg.C)), dtype=cond.t.dtype, device=cond.t.device)
-                E.concat_channels(ctx, [cond, self._fake_seg.detach()], out=both[:nb])
-                E.concat_channels(ctx, [cond, self._Bseg], out=both[nb:])
-                preds.append(getattr(self, 'net' + n).run(ctx, E.Act(both, cond.C + self._fake_seg.C)))
-            pred = E.weighted_sum(ctx, preds, self.seg_weights[:M + 1])
-            E.loss_op_halves(ctx, cs.kind, pred, (cs.target(False), cs.target(True)), 0.5 * wD[M],
-                             (getattr(self, f'loss_D_fake_{S}').view(1), getattr(self, f'loss_D_real_{S}').view(1)))
-        elif self.seg_gen:
-            pred = self._seg_pred(ctx, self._fake_seg.detach())
-            E.loss_op(ctx, cs.kind, pred, None, cs.target(False), 0.5 * wD[M], getattr(self, f'loss_D_fake_{S}').view(1))
-        real_mod, real_seg = self._pairs_real(ctx) if ((self.seg_gen and not paired_seg) or not real_mod_done) else (None, None)
-        for i, n in enumerate(self.model_names_d):
-            if real_mod_done:
-                break
-            with self._branch(i):
-                pred = getattr(self, 'net' + n).run(ctx, real_mod[i])
-                E.loss_op(ctx, cg.kind, pred, None, cg.target(True), 0.5 * wD[i], getattr(self, f'loss_D_real_{i + 1}').view(1))
-        if self.seg_gen and not paired_seg:
-            preds = [getattr(self, 'net' + n).run(ctx, real_seg[i]) for i, n in enumerate(self.model_names_ds)]
-            pred = E.weighted_sum(ctx, preds, self.seg_weights[:M + 1])
-            E.loss_op(ctx, cs.kind, pred, None, cs.target(True), 0.5 * wD[M], getattr(self, f'loss_D_real_{S}').view(1))
+        self._discriminator_pass(tape, ctx, jobs, cached_real=lambda: self._pairs_real(ctx))
         tape.backward()
         self._join()
 
@@ -718,15 +775,15 @@ class DeepLIIFModel(BaseModel):
             with self._branch(i):
                 pair = E.concat_channels(ctx, [self._A, self._fake[i]])
                 pred = getattr(self, 'net' + n).run(ctx, pair)
-                E.loss_op(ctx, cg.kind, pred, None, cg.target(True), wG[i], getattr(self, f'loss_G_GAN_{i + 1}').view(1))
+                E.loss_op(ctx, cg.kind, pred, None, cg.target(True), wG[i], self._slot(f'G_GAN_{i + 1}'))
         if self.seg_gen:
             pred = self._seg_pred(ctx, self._fake_seg)
-            E.loss_op(ctx, cs.kind, pred, None, cs.target(True), wG[M - 1], getattr(self, f'loss_G_GAN_{S}').view(1))
+            E.loss_op(ctx, cs.kind, pred, None, cs.target(True), wG[M - 1], self._slot(f'G_GAN_{S}'))
         for i in range(M):
             with self._branch(i):
-                E.loss_op(ctx, L.LOSS_SMOOTH_L1, self._fake[i], self._B[i], 0.0, wG[i] * self.lambda_L1, self._l1_raw(i))
+                E.loss_op(ctx, L.LOSS_SMOOTH_L1, self._fake[i], self._B[i], 0.0, wG[i] * self.lambda_L1, self._slot(f'G_L1_{i + 1}'))
         if self.seg_gen:
-            E.loss_op(ctx, L.LOSS_SMOOTH_L1, self._fake_seg, self._Bseg, 0.0, wG[M - 1] * self.lambda_L1, self._l1_raw(M))
+            E.loss_op(ctx, L.LOSS_SMOOTH_L1, self._fake_seg, self._Bseg, 0.0, wG[M - 1] * self.lambda_L1, self._slot(f'G_L1_{S}'))
         if self.criterionVGG is not None:
             # DeepLIIF_model.py:406-421: loss_G_VGG_i * lambda_feat joins the modality terms; the seg image's VGG value is computed there
             # too (:408-409) but never added to loss_G (:418-421), so it is not evaluated here
@@ -736,8 +793,7 @@ class DeepLIIFModel(BaseModel):
         tape.backward()
         self._join()
         self._tape_G = None
-        # the reference logs loss_G_L1 already multiplied by lambda_L1 (:398-400)
-        self._loss_buf[self._l1_slots] *= self.lambda_L1
+        self._scale_reported('_L1_', self.lambda_L1)
         if self.criterionVGG is not None:
             self._vgg_buf *= self.lambda_feat
             for i in range(M):
@@ -746,48 +802,9 @@ class DeepLIIFModel(BaseModel):
     def _extra_g_terms(self, ctx):
         """further terms of loss_G on the generator tape, before its backward (DeepLIIFKD: the distillation terms)"""
 
-    def _l1_raw(self, i):
-        M, S = self.opt.modalities_no, self.mod_id_seg
-        name = f'G_L1_{i + 1}' if i < M else f'G_L1_{S}'
-        return self._loss_buf[self._loss_index[name]].view(1)
-
-    @property
-    def _l1_slots(self):
-        if not hasattr(self, '_l1_slots_cache'):
-            idx = [self._loss_index[n] for n in self.loss_names if n.startswith('G_L1_')]
-            self._l1_slots_cache = torch.tensor(idx, dtype=torch.long, device=self.device)
-        return self._l1_slots_cache
-
     # ---------------------------------------------------------------------------------------------------------
     def _d_nets(self):
         return [getattr(self, 'net' + n) for n in self.model_names_d + self.model_names_ds]
-
-    def optimize_parameters(self):
-        """DeepLIIF_model.py:431-467."""
-        self._sync_replicas()
-        self.forward()
-        self.set_requires_grad(self._d_nets(), True)
-        self.optimizer_D.zero_grad()
-        self.exchange.begin(self.optimizer_D)
-        self.backward_D()
-        self.exchange.finish(self.optimizer_D)       # cannot hide: D must be updated before backward_G runs it (DeepLIIF_model.py:431-467)
-        self.optimizer_D.step()
-        self.set_requires_grad(self._d_nets(), False)
-        self.optimizer_G.zero_grad()
-        self.exchange.begin(self.optimizer_G)
-        self.backward_G()                            # each generator's slice goes on the wire as soon as its backward is done
-        self.exchange.finish(self.optimizer_G)
-        self.optimizer_G.step()
-
-    def calculate_losses(self):
-        """DeepLIIF_model.py:469-507: losses + gradients without the optimizer steps (validation)."""
-        self.forward()
-        self.set_requires_grad(self._d_nets(), True)
-        self.optimizer_D.zero_grad()
-        self.backward_D()
-        self.set_requires_grad(self._d_nets(), False)
-        self.optimizer_G.zero_grad()
-        self.backward_G()
 
 
 class DeepLIIFExtModel(BaseModel):
@@ -850,14 +867,7 @@ class DeepLIIFExtModel(BaseModel):
             self.lambda_L1 = _get(opt, 'lambda_L1', 100.0)
             params_g = [p for net in self.netG + [n for n in self.netGS if n is not None] for p in net.parameters()]
             params_d = [p for net in self.netD + [n for n in self.netDS if n is not None] for p in net.parameters()]
-            OptCls = networks.get_optimizer(_get(opt, 'optimizer', 'adam'))
-            try:
-                self.optimizer_G = OptCls(params_g, lr=opt.lr_g, betas=(opt.beta1, 0.999))
-                self.optimizer_D = OptCls(params_d, lr=opt.lr_d, betas=(opt.beta1, 0.999))
-            except TypeError:
-                self.optimizer_G = OptCls(params_g, lr=opt.lr_g)
-                self.optimizer_D = OptCls(params_d, lr=opt.lr_d)
-            self.optimizers += [self.optimizer_G, self.optimizer_D]
+            self._make_optimizers(params_g, params_d, opt)
             self.exchange = GradExchanger()
         self._tape_G = None
         # branch streams (round 5): chain i = G_i -> [cat(A, fake_1, fake_i) on the main stream] -> GS_i, with D_i / DS_i, runs on stream i % DL_STREAMS.
@@ -870,9 +880,6 @@ class DeepLIIFExtModel(BaseModel):
 
     def _input_channels(self, opt):
         return opt.input_nc
-
-    def _slot(self, name):
-        return self._loss_buf[self._loss_index[name]].view(1)
 
     def set_input(self, input):
         """DeepLIIFExt_model.py:134-158: dict{'A', 'B': list, 'BS': list, 'A_paths'}  (SDG: 'A' is a list of input modalities,
@@ -891,7 +898,7 @@ class DeepLIIFExtModel(BaseModel):
     def forward(self, record=None):
         record = self.is_train if record is None else record
         tape = self._new_tape() if record else None
-        ctx = E.Ctx(self.precision, self._hook_tape(tape), training=record)
+        ctx = self._ctx(tape, training=record)
         self._fake, self.fake_B = [], []
         self._fork()
         for i, net in enumerate(self.netG):
@@ -925,62 +932,23 @@ class DeepLIIFExtModel(BaseModel):
 
     def backward_D(self):
         tape = self._new_tape()
-        ctx = E.Ctx(self.precision, self._hook_tape(tape), training=True)
-        cg, cs, M = self.criterionGAN_mod, self.criterionGAN_seg, self.mod_gen_no
+        ctx = self._ctx(tape)
         rc = self._cat_real(ctx)                     # (main stream, before the fork)
+        paired = _D_PAIR_BATCH and all(_pairable(d) for d in self._d_nets())         # all or nothing over both families
+        jobs = [DJob(i, [d], [[self._A, self._fake[i].detach()]], [[self._A, self._B[i]]], self.criterionGAN_mod, 0.5 * self.loss_D_weights[i],
+                     (self._slot(f'D_fake_{i + 1}'), self._slot(f'D_real_{i + 1}')), paired=paired) for i, d in enumerate(self.netD)]
+        jobs += [DJob(i, [self.netDS[i]], [[rc[i], f.detach()]], [[rc[i], self._BS[i]]], self.criterionGAN_seg, 0.5 * self.loss_DS_weights[i],
+                      (self._slot(f'DS_fake_{i + 1}'), self._slot(f'DS_real_{i + 1}')), paired=paired) for i, f in enumerate(self._fake_s)]
         self._fork()                                 # (the gradients were zeroed on the main stream)
-        if _D_PAIR_BATCH and all(_pairable(d) for d in list(self.netD[:M]) + [d for d in self.netDS if d is not None]):
-            # per-sample-normalised discriminators: the fake and the real inputs of each as ONE batch of 2N (see DeepLIIFModel.backward_D)
-            def both_halves(parts_fake, parts_real):
-                nb, h, w, _ = parts_fake[0].t.shape
-                c = sum(p.C for p in parts_fake)
-                both = torch.zeros((2 * nb, h, w, E.cpad(c)), dtype=parts_fake[0].t.dtype, device=parts_fake[0].t.device)
-                E.concat_channels(ctx, parts_fake, out=both[:nb])
-                E.concat_channels(ctx, parts_real, out=both[nb:])
-                return E.Act(both, c)
-            for i in range(M):
-                with self._branch(i):
-                    self._mark_net(tape, self.netD[i])
-                    pred = self.netD[i].run(ctx, both_halves([self._A, self._fake[i].detach()], [self._A, self._B[i]]))
-                    E.loss_op_halves(ctx, cg.kind, pred, (cg.target(False), cg.target(True)), 0.5 * self.loss_D_weights[i],
-                                     (self._slot(f'D_fake_{i + 1}'), self._slot(f'D_real_{i + 1}')))
-            for i in range(len(self._fake_s)):
-                with self._branch(i):
-                    self._mark_net(tape, self.netDS[i])
-                    pred = self.netDS[i].run(ctx, both_halves([rc[i], self._fake_s[i].detach()], [rc[i], self._BS[i]]))
-                    E.loss_op_halves(ctx, cs.kind, pred, (cs.target(False), cs.target(True)), 0.5 * self.loss_DS_weights[i],
-                                     (self._slot(f'DS_fake_{i + 1}'), self._slot(f'DS_real_{i + 1}')))
-            tape.backward()
-            self._join()
-            return
-        for i in range(M):
-            with self._branch(i):
-                # every discriminator runs twice below (fake, real): mark before the first use, on the stream of its branch (the marker's all-reduce is
-                # ordered behind THAT stream)
-                self._mark_net(tape, self.netD[i])
-                pred = self.netD[i].run(ctx, E.concat_channels(ctx, [self._A, self._fake[i].detach()]))
-                E.loss_op(ctx, cg.kind, pred, None, cg.target(False), 0.5 * self.loss_D_weights[i], self._slot(f'D_fake_{i + 1}'))
-        for i in range(len(self._fake_s)):
-            with self._branch(i):
-                self._mark_net(tape, self.netDS[i])
-                pred = self.netDS[i].run(ctx, E.concat_channels(ctx, [rc[i], self._fake_s[i].detach()]))
-                E.loss_op(ctx, cs.kind, pred, None, cs.target(False), 0.5 * self.loss_DS_weights[i], self._slot(f'DS_fake_{i + 1}'))
-        for i in range(M):
-            with self._branch(i):
-                pred = self.netD[i].run(ctx, E.concat_channels(ctx, [self._A, self._B[i]]))
-                E.loss_op(ctx, cg.kind, pred, None, cg.target(True), 0.5 * self.loss_D_weights[i], self._slot(f'D_real_{i + 1}'))
-        for i in range(len(self._fake_s)):
-            with self._branch(i):
-                pred = self.netDS[i].run(ctx, E.concat_channels(ctx, [rc[i], self._BS[i]]))
-                E.loss_op(ctx, cs.kind, pred, None, cs.target(True), 0.5 * self.loss_DS_weights[i], self._slot(f'DS_real_{i + 1}'))
+        self._discriminator_pass(tape, ctx, jobs)
         tape.backward()
         self._join()
 
     def backward_G(self):
         tape = self._tape_G
-        ctx = E.Ctx(self.precision, self._hook_tape(tape), training=True)
+        ctx = self._ctx(tape)
         cg, M = self.criterionGAN_mod, self.mod_gen_no
-        rc = self._cat_real(E.Ctx(self.precision, None, training=True))
+        rc = self._cat_real(self._ctx(None))
         self._fork()                                 # (D was updated and repacked, the G gradients zeroed, on the main stream)
         for i in range(M):
             with self._branch(i):
@@ -1003,46 +971,11 @@ class DeepLIIFExtModel(BaseModel):
         tape.backward()
         self._join()
         self._tape_G = None
-        # index tensors built ONCE: torch.tensor(..., device=cuda) is a host-to-device copy per step (and not capturable, models.StepGraph)
-        if not hasattr(self, '_idx_cache'):
-            self._idx_cache = {k: torch.tensor([self._loss_index[n] for n in self.loss_names if k in n], dtype=torch.long, device=self.device)
-                               for k in ('_L1_', '_VGG_')}
-        self._loss_buf[self._idx_cache['_L1_']] *= self.lambda_L1
-        if self._idx_cache['_VGG_'].numel():
-            # reported like the reference does (value * lambda_feat); NaN, not a plausible-looking 0.0, when the term was not evaluated
-            sel = self._idx_cache['_VGG_']
-            if vgg is not None:
-                self._loss_buf[sel] *= self.lambda_feat
-            else:
-                self._loss_buf[sel] = float('nan')
+        self._scale_reported('_L1_', self.lambda_L1)
+        self._scale_reported('_VGG_', self.lambda_feat if vgg is not None else None)      # (SDG's slots; DeepLIIFExt has none)
 
     def _d_nets(self):
         return [n for n in self.netD + self.netDS if n is not None]
-
-    def optimize_parameters(self):
-        self._sync_replicas()
-        self.forward()
-        self.set_requires_grad(self._d_nets(), True)
-        self.optimizer_D.zero_grad()
-        self.exchange.begin(self.optimizer_D)
-        self.backward_D()
-        self.exchange.finish(self.optimizer_D)       # cannot hide: D must be updated before backward_G runs it (DeepLIIF_model.py:431-467)
-        self.optimizer_D.step()
-        self.set_requires_grad(self._d_nets(), False)
-        self.optimizer_G.zero_grad()
-        self.exchange.begin(self.optimizer_G)
-        self.backward_G()                            # each generator's slice goes on the wire as soon as its backward is done
-        self.exchange.finish(self.optimizer_G)
-        self.optimizer_G.step()
-
-    def calculate_losses(self):
-        self.forward()
-        self.set_requires_grad(self._d_nets(), True)
-        self.optimizer_D.zero_grad()
-        self.backward_D()
-        self.set_requires_grad(self._d_nets(), False)
-        self.optimizer_G.zero_grad()
-        self.backward_G()
 
 
 class SDGModel(DeepLIIFExtModel):
@@ -1117,8 +1050,6 @@ class DeepLIIFKDModel(DeepLIIFModel):
         self._loss_buf = torch.zeros(len(slots), dtype=torch.float32, device=self.device)
         for n, i in self._loss_index.items():
             setattr(self, 'loss_' + n, self._loss_buf[i])
-        if hasattr(self, '_l1_slots_cache'):
-            del self._l1_slots_cache
         if not self.is_train:
             self.visual_names = [n for n in self.visual_names if not n.endswith('_teacher')]
             return
@@ -1159,7 +1090,7 @@ class DeepLIIFKDModel(DeepLIIFModel):
 
     def _extra_g_terms(self, ctx):
         M, S, f = self.opt.modalities_no, self.mod_id_seg, self.FACTOR_KLDIV
-        slot = lambda n: self._loss_buf[self._loss_index[n]].view(1)
+        slot = self._slot
         for i in range(M):
             E.kldiv_op(ctx, self._fake[i], self._teacher[f'fake_B_{i + 1}_teacher'], f, slot(f'G_KLDiv_{i + 1}'))
         E.kldiv_op(ctx, self._fake_seg, self._teacher[f'fake_B_{S}_teacher'], f, slot(f'G_KLDiv_{S}'))
@@ -1256,14 +1187,7 @@ class CycleGANModel(BaseModel):
             self.criterionVGG = self._make_cycle_vgg(opt)
             params_g = [p for net in self.netGA + self.netGB for p in net.parameters()]
             params_d = [p for net in self.netDA + self.netDB for p in net.parameters()]
-            OptCls = networks.get_optimizer(_get(opt, 'optimizer', 'adam'))
-            try:
-                self.optimizer_G = OptCls(params_g, lr=opt.lr_g, betas=(opt.beta1, 0.999))
-                self.optimizer_D = OptCls(params_d, lr=opt.lr_d, betas=(opt.beta1, 0.999))
-            except TypeError:
-                self.optimizer_G = OptCls(params_g, lr=opt.lr_g)
-                self.optimizer_D = OptCls(params_d, lr=opt.lr_d)
-            self.optimizers += [self.optimizer_G, self.optimizer_D]
+            self._make_optimizers(params_g, params_d, opt)
             self.exchange = GradExchanger()
         self._tape_G = None
 
@@ -1294,7 +1218,7 @@ class CycleGANModel(BaseModel):
         """CycleGAN_model.py:161-170; with only one direction loaded (test time) the other lists stay empty"""
         record = self.is_train if record is None else record
         tape = E.Tape() if record else None
-        ctx = E.Ctx(self.precision, self._hook_tape(tape), training=record)
+        ctx = self._ctx(tape, training=record)
         for net in self.netGA + self.netGB:            # every generator runs twice below: mark before the first use
             self._mark_net(tape, net)
         self._fake_B = [net.run(ctx, self._A) for net in self.netGA]
@@ -1308,14 +1232,11 @@ class CycleGANModel(BaseModel):
                 setattr(self, f'{fam}_{i + 1}', t)
         self._tape_G = tape
 
-    def _slot(self, name):
-        return self._loss_buf[self._loss_index[name]].view(1)
-
     def backward_G(self):
         """CycleGAN_model.py:207-264"""
         tape = self._tape_G
         assert tape is not None, 'forward() must run in training mode before backward_G()'
-        ctx = E.Ctx(self.precision, self._hook_tape(tape), training=True)
+        ctx = self._ctx(tape)
         cg, wG, cyc = self.criterionGAN, self.loss_G_weights, self.loss_cyc_weights
         for n in ('G_A', 'G_B', 'cycle_A', 'cycle_B'):           # the terms below ACCUMULATE into their slots (sums over the modalities)
             self._slot(n).zero_()
@@ -1341,7 +1262,7 @@ class CycleGANModel(BaseModel):
         cg = self.criterionGAN
         for i, (net, real, fake) in enumerate(zip(nets, reals, fakes)):
             tape = E.Tape()
-            ctx = E.Ctx(self.precision, self._hook_tape(tape), training=True)
+            ctx = self._ctx(tape)
             self._mark_net(tape, net)
             w = 0.5 * self.loss_D_weights[i]
             E.loss_op(ctx, cg.kind, net.run(ctx, real), None, cg.target(True), w, slot, w, True)
@@ -1366,18 +1287,9 @@ class CycleGANModel(BaseModel):
         self._sync_replicas()
         self.forward()
         self.set_requires_grad(self._d_nets(), False)
-        self.optimizer_G.zero_grad()
-        self.exchange.begin(self.optimizer_G)
-        self.backward_G()
-        self.exchange.finish(self.optimizer_G)
-        self.optimizer_G.step()
+        self._update(self.optimizer_G, self.backward_G)
         self.set_requires_grad(self._d_nets(), True)
-        self.optimizer_D.zero_grad()
-        self.exchange.begin(self.optimizer_D)
-        self.backward_D_A()
-        self.backward_D_B()
-        self.exchange.finish(self.optimizer_D)
-        self.optimizer_D.step()
+        self._update(self.optimizer_D, self.backward_D_A, self.backward_D_B)
 
 
 _MODEL_CLASSES = {'DeepLIIF': DeepLIIFModel, 'DeepLIIFExt': DeepLIIFExtModel, 'SDG': SDGModel, 'DeepLIIFKD': DeepLIIFKDModel, 'CycleGAN': CycleGANModel}

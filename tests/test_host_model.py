@@ -354,3 +354,82 @@ def test_paired_discriminator_batch_equals_the_two_calls(monkeypatch):
     model.forward()
     model.backward_D()
     assert calls == [2, 2]
+
+
+def test_paired_discriminator_batch_equals_the_two_calls_ext(monkeypatch):
+    """The same for DeepLIIFExtModel with seg generators (D_i and DS_i, all-or-nothing over both families): the paired batch against the two calls, losses
+    within 1e-6 * max(1, |v|) and discriminator gradients within 1e-5 relative L2.  Measured on the emulated backend (fp32): all eight losses equal to the
+    last bit, gradients 3.0e-7 apart (summation order of the weight gradients)."""
+    A = seeded_uniform((2, 3, 64, 64), 22)
+    B = [seeded_uniform((2, 3, 64, 64), 23 + i) for i in range(2)]
+    BS = [seeded_uniform((2, 3, 64, 64), 43 + i) for i in range(2)]
+
+    def make(norm):
+        torch.manual_seed(0)
+        opt = make_opt(2, True, norm)
+        opt.model, opt.net_ds = 'DeepLIIFExt', 'n_layers'
+        opt.loss_G_weights = opt.loss_D_weights = opt.seg_weights = [0.5, 0.5]
+        model = CpuExtModel(opt)
+        model.setup(opt)
+        model.set_input({'A': A, 'B': B, 'BS': BS, 'A_paths': ['x']})
+        return model
+    res = {}
+    for paired in (False, True):
+        monkeypatch.setattr(M, '_D_PAIR_BATCH', paired)
+        model = make('instance')
+        model.forward()
+        for o in model.optimizers:
+            o.zero_grad()
+        model.backward_D()
+        losses = {k: float(v) for k, v in model.get_current_losses().items() if k.startswith('D')}
+        grads = torch.cat([p.grad.reshape(-1) for d in model._d_nets() for p in d.parameters()])
+        res[paired] = (losses, grads.clone())
+    assert sorted(res[True][0]) == sorted(f'{fam}_{kind}_{i}' for fam in ('D', 'DS') for kind in ('real', 'fake') for i in (1, 2))
+    assert res[False][0].keys() == res[True][0].keys()
+    for k, v in res[False][0].items():
+        print(k, v, res[True][0][k], abs(res[True][0][k] - v))
+        assert abs(res[True][0][k] - v) <= 1e-6 * max(1.0, abs(v)), (k, v, res[True][0][k])
+    g0, g1 = res[False][1], res[True][1]
+    print('relative L2 distance of the discriminator gradients', float((g0 - g1).norm() / g0.norm()))
+    assert float((g0 - g1).norm() / g0.norm()) < 1e-5 and float(g0.norm()) > 0
+    # BatchNorm discriminators keep the two calls of batch N each, whatever the switch says
+    monkeypatch.setattr(M, '_D_PAIR_BATCH', True)
+    model = make('batch')
+    calls = {}
+    for name, d in [(f'D_{i + 1}', d) for i, d in enumerate(model.netD)] + [(f'DS_{i + 1}', d) for i, d in enumerate(model.netDS)]:
+        d.run = lambda ctx, x, name=name, orig=d.run: (calls.setdefault(name, []).append(x.t.shape[0]), orig(ctx, x))[1]
+    model.forward()
+    model.backward_D()
+    assert calls == {n: [2, 2] for n in ('D_1', 'D_2', 'DS_1', 'DS_2')}
+
+
+def test_two_call_discriminator_pass_runs_every_fake_before_every_real(monkeypatch):
+    """The two-call route (BatchNorm discriminators) of DeepLIIFModel.backward_D: all modality fakes, all seg fakes, all modality reals, all seg reals, every call
+    on a batch of N.  That order is what the BatchNorm running statistics and the overlap of the data-parallel exchange depend on."""
+    monkeypatch.setattr(M, '_D_PAIR_BATCH', True)
+    torch.manual_seed(0)
+    opt = make_opt(2, True, 'batch')
+    model = CpuModel(opt)
+    model.setup(opt)
+    model.set_input({'A': seeded_uniform((2, 3, 64, 64), 22), 'B': [seeded_uniform((2, 3, 64, 64), 23 + i) for i in range(3)], 'A_paths': ['x']})
+    model.forward()
+    calls = []
+    targets = dict(zip(model.model_names_d, model._B))
+    targets.update({n: model._Bseg for n in model.model_names_ds})
+
+    def wrap(name, d):
+        orig = d.run
+
+        def run(ctx, x):
+            # the image half of the pair (the channels behind the 3 of the condition) is the real target or a generated image
+            side = 'real' if torch.equal(x.t[..., 3:6], targets[name].t[..., :3]) else 'fake'
+            calls.append((name, side, x.t.shape[0]))
+            return orig(ctx, x)
+        d.run = run
+    for n in model.model_names_d + model.model_names_ds:
+        wrap(n, getattr(model, 'net' + n))
+    model.backward_D()
+    S = model.mod_id_seg
+    mod, seg = ['D1', 'D2'], [f'D{S}0', f'D{S}1', f'D{S}2']
+    assert (mod, seg) == (model.model_names_d, model.model_names_ds)
+    assert calls == [(n, 'fake', 2) for n in mod + seg] + [(n, 'real', 2) for n in mod + seg]
