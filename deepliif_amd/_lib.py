@@ -20,7 +20,7 @@ NORM_INSTANCE, NORM_BATCH = 0, 1
 LOSS_BCE_LOGITS, LOSS_MSE, LOSS_SMOOTH_L1, LOSS_L1, LOSS_LINEAR = 0, 1, 2, 3, 4
 MAX_TAPS, MAX_PHASES = 64, 4
 WGRAD_MULTI_MAX = 24
-DL_VERSION = 115
+DL_VERSION = 116
 
 i32 = C.c_int32
 
@@ -142,6 +142,9 @@ SIGNATURES = {
     'dl_tile_gather_u8': (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _i, _i, C.c_uint32, _vp, _i, _vp, _i, _i, _vp]),
     'dl_tile_gray_stats_u8': (_i, [_vp, _i64, _i, _i, _vp, _i, _i, _i, C.c_uint32, _vp, _vp]),
     'dl_tile_paste_u8': (_i, [_i, _vp, _i, _i, _vp, _i, _vp, _i64, _vp]),
+    'dl_tile_resample_supported': (_i, [_i, _i]),
+    'dl_tile_gather_resample_u8': (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _i, _i, C.c_uint32, _i, _vp, _vp, _i, _i, _vp, _i, _vp, _i, _i, _vp]),
+    'dl_tile_paste_resample_u8': (_i, [_i, _vp, _i, _i, _i, _vp, _vp, _i, _i, _vp, _i, _vp, _i64, _vp]),
     'dl_probe_mfma16': (_i, [_vp, _vp, _vp, _vp]),
     'dl_probe_trread': (_i, [_vp, _vp, _vp]),
     'dl_probe_mfma_sustained_elems': (C.c_size_t, [_i]),

@@ -119,6 +119,176 @@ __global__ void tile_paste_kernel(const T *__restrict__ tiles, int in_pstride, i
     }
 }
 
+// ---- resampled tiles (tile_size != scale_size): PIL's Image.resize (separable bicubic, 8-bit fixed point) either side of the network, bit for bit.
+// The coefficient table comes from the caller (deepliif_amd/tiling.py resample_table: bounds[xx] = {xmin, n}, kk[xx][ksize]); the kernels only apply it:
+// byte = clip((2^21 + sum pixel * k) >> 22), horizontal pass first, its uint8 result read by the vertical pass.  One workgroup owns one tile and a
+// strip of R output rows: it runs the horizontal pass for the source rows the strip's vertical taps reach (bounds[first].xmin .. bounds[last].xmin + n)
+// into an LDS byte image (one r | g << 8 | b << 16 word per pixel), barriers, and runs the vertical pass from LDS into the store.
+#define DL_RS_BITS 22
+#define DL_RS_LDS_BYTES 65536
+#define DL_RS_MAX_STRIP 32        // upper end of R: more strips per tile than the LDS budget alone would give, so that a batch of 8 tiles fills the CUs
+
+struct RsTable {
+    const int32_t *bounds;
+    const int32_t *kk;
+    int ksize;
+};
+
+// taps of output coordinate xx; clamped so that a malformed table cannot turn into an out-of-range read
+__device__ __forceinline__ void rs_taps(const RsTable &tb, int xx, int in, int &x0, int &n) {
+    x0 = tb.bounds[2 * xx];
+    n = tb.bounds[2 * xx + 1];
+    x0 = x0 < 0 ? 0 : (x0 > in ? in : x0);
+    const int most = tb.ksize < in - x0 ? tb.ksize : in - x0;
+    n = n < 0 ? 0 : (n > most ? most : n);
+}
+
+__device__ __forceinline__ uint32_t rs_clip8(int acc) {
+    const int v = acc >> DL_RS_BITS;
+    return (uint32_t)(v < 0 ? 0 : (v > 255 ? 255 : v));
+}
+
+__device__ __forceinline__ uint32_t rs_pack(int a0, int a1, int a2) { return rs_clip8(a0) | (rs_clip8(a1) << 8) | (rs_clip8(a2) << 16); }
+
+// vertical pass of output pixel (yy, xx) over the LDS image `mid` (row 0 = source row `ya`, `rows` rows of `stride` words)
+__device__ __forceinline__ uint32_t rs_vertical(const RsTable &tb, const uint32_t *mid, int stride, int ya, int rows, int yy, int xx, int in) {
+    int v0, n;
+    rs_taps(tb, yy, in, v0, n);
+    int r0 = v0 - ya;
+    if (r0 < 0) r0 = 0;
+    if (n > rows - r0) n = rows - r0;
+    const int32_t *k = tb.kk + (long long)yy * tb.ksize;
+    int a0 = 1 << (DL_RS_BITS - 1), a1 = a0, a2 = a0;
+    for (int j = 0; j < n; ++j) {
+        const uint32_t m = mid[(r0 + j) * stride + xx];
+        const int kj = k[j];
+        a0 += (int)(m & 0xff) * kj;
+        a1 += (int)((m >> 8) & 0xff) * kj;
+        a2 += (int)((m >> 16) & 0xff) * kj;
+    }
+    return rs_pack(a0, a1, a2);
+}
+
+template <typename T>
+__global__ void __launch_bounds__(256) tile_gather_resample_kernel(TileSrc src, int n_src, int H0, int W0, const int32_t *__restrict__ origins, int tile, int pad,
+                                                                   uint32_t pad_rgb, int net, RsTable tb, int R, int rows_cap, const float *__restrict__ lut,
+                                                                   T *__restrict__ out, int out_pstride, int out_cp) {
+    extern __shared__ uint32_t rs_lds[];
+    uint32_t *mid = rs_lds;                          // [rows_cap][net]: horizontally resized source rows of the current image
+    uint32_t *done = rs_lds + rows_cap * net;        // [n_src - 1][R][net]: finished strips of the earlier images, until all channels of a pixel are stored together
+    const int t = blockIdx.y;
+    const int y0 = blockIdx.x * R, y1 = y0 + R < net ? y0 + R : net;
+    if (y0 >= y1) return;
+    const int ox = origins[2 * t], oy = origins[2 * t + 1];
+    const int patch = tile - 2 * pad;
+    int ya, na, yb, nb;
+    rs_taps(tb, y0, tile, ya, na);
+    rs_taps(tb, y1 - 1, tile, yb, nb);
+    int rows = yb + nb - ya;
+    rows = rows < 0 ? 0 : (rows > rows_cap ? rows_cap : rows);
+    for (int s = 0; s < n_src; ++s) {
+        const uint8_t *img = src.img[0];
+        long long row_stride = src.row_stride[0];
+#pragma unroll
+        for (int q = 1; q < DL_TILE_MAX_SRC; ++q)
+            if (q == s) { img = src.img[q]; row_stride = src.row_stride[q]; }
+        if (s) __syncthreads();                      // the vertical pass of the previous image has finished reading mid
+        for (int i = threadIdx.x; i < rows * net; i += blockDim.x) {
+            const int row = i / net, xx = i - row * net;
+            int x0, n;
+            rs_taps(tb, xx, tile, x0, n);
+            const int32_t *k = tb.kk + (long long)xx * tb.ksize;
+            int a0 = 1 << (DL_RS_BITS - 1), a1 = a0, a2 = a0;
+            for (int j = 0; j < n; ++j) {
+                int r, g, b;
+                tile_pixel(img, row_stride, H0, W0, ox, oy, ya + row, x0 + j, patch, pad, pad_rgb, r, g, b);
+                const int kj = k[j];
+                a0 += r * kj; a1 += g * kj; a2 += b * kj;
+            }
+            mid[i] = rs_pack(a0, a1, a2);
+        }
+        __syncthreads();
+        for (int i = threadIdx.x; i < (y1 - y0) * net; i += blockDim.x) {
+            const int ry = i / net, xx = i - ry * net;
+            const uint32_t word = rs_vertical(tb, mid, net, ya, rows, y0 + ry, xx, tile);
+            if (s + 1 < n_src) {
+                done[(s * R + ry) * net + xx] = word;        // read back below by this same thread
+                continue;
+            }
+            T *o = out + (((long long)t * net + (y0 + ry)) * net + xx) * out_pstride;
+            for (int c8 = 0; c8 < out_cp; c8 += 8) {
+                float v[8];
+#pragma unroll
+                for (int j = 0; j < 8; ++j) v[j] = 0.f;
+#pragma unroll
+                for (int q = 0; q < DL_TILE_MAX_SRC; ++q) {
+                    const int c = 3 * q;                      // channels 3q .. 3q+2 of the concatenated input
+                    if (q < n_src && c + 2 >= c8 && c < c8 + 8) {
+                        const uint32_t m = q + 1 < n_src ? done[(q * R + ry) * net + xx] : word;
+#pragma unroll
+                        for (int kc = 0; kc < 3; ++kc) {
+                            const int cc = c + kc - c8;
+                            if (cc >= 0 && cc < 8) v[cc] = lut[(m >> (8 * kc)) & 0xff];
+                        }
+                    }
+                }
+                Vec8<T>::store(o + c8, v);
+            }
+        }
+    }
+}
+
+// tensor2im byte of one activation value, in the exact form of tile_paste_kernel
+__device__ __forceinline__ int tensor2im_u8(float x) { return (int)(uint8_t)(int)__fmul_rn(__fmul_rn(__fadd_rn(x, 1.0f), 0.5f), 255.0f); }
+
+template <typename T>
+__global__ void __launch_bounds__(256) tile_paste_resample_kernel(const T *__restrict__ tiles, int in_pstride, int net, int tile, RsTable tb, int R, int rows_cap,
+                                                                  const int32_t *__restrict__ rects, uint8_t *__restrict__ dst, long long dst_row_stride) {
+    extern __shared__ uint32_t rs_lds[];             // [rows_cap][tile]: tensor2im bytes of the activation rows, horizontally resized (columns l .. l+w-1 used)
+    const int32_t *rc = rects + 8 * blockIdx.y;
+    const int slot = rc[0], l = rc[1], tp = rc[2], w = rc[3], h = rc[4], px = rc[5], py = rc[6];
+    const uint32_t rgb = (uint32_t)rc[7];
+    if (l < 0 || tp < 0 || w <= 0 || h <= 0 || l + w > tile || tp + h > tile) return;          // not a window of the tile
+    const int y0 = tp + blockIdx.x * R, y1 = y0 + R < tp + h ? y0 + R : tp + h;
+    if (y0 >= y1) return;
+    if (slot < 0) {
+        for (int i = threadIdx.x; i < (y1 - y0) * w; i += blockDim.x) {
+            const int ry = i / w, x = i - ry * w;
+            uint8_t *o = dst + (long long)(py + y0 - tp + ry) * dst_row_stride + 3ll * (px + x);
+            o[0] = rgb & 0xff; o[1] = (rgb >> 8) & 0xff; o[2] = (rgb >> 16) & 0xff;
+        }
+        return;
+    }
+    int ya, na, yb, nb;
+    rs_taps(tb, y0, net, ya, na);
+    rs_taps(tb, y1 - 1, net, yb, nb);
+    int rows = yb + nb - ya;
+    rows = rows < 0 ? 0 : (rows > rows_cap ? rows_cap : rows);
+    const T *base = tiles + (long long)slot * net * net * in_pstride;
+    for (int i = threadIdx.x; i < rows * w; i += blockDim.x) {
+        const int row = i / w, xx = l + (i - row * w);
+        int x0, n;
+        rs_taps(tb, xx, net, x0, n);
+        const int32_t *k = tb.kk + (long long)xx * tb.ksize;
+        const T *p = base + ((long long)(ya + row) * net + x0) * in_pstride;
+        int a0 = 1 << (DL_RS_BITS - 1), a1 = a0, a2 = a0;
+        for (int j = 0; j < n; ++j) {
+            float v[8];
+            Vec8<T>::load(p + (long long)j * in_pstride, v);
+            const int kj = k[j];
+            a0 += tensor2im_u8(v[0]) * kj; a1 += tensor2im_u8(v[1]) * kj; a2 += tensor2im_u8(v[2]) * kj;
+        }
+        rs_lds[row * tile + xx] = rs_pack(a0, a1, a2);
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < (y1 - y0) * w; i += blockDim.x) {
+        const int ry = i / w, x = i - ry * w;
+        const uint32_t m = rs_vertical(tb, rs_lds, tile, ya, rows, y0 + ry, l + x, net);
+        uint8_t *o = dst + (long long)(py + y0 - tp + ry) * dst_row_stride + 3ll * (px + x);
+        o[0] = m & 0xff; o[1] = (m >> 8) & 0xff; o[2] = (m >> 16) & 0xff;
+    }
+}
+
 // tiles / rectangles per launch (gridDim.y <= 65535); DL_TILE_GRID_Y=<n> overrides it so that the chunked path can be tested on small regions
 static int tile_grid_y() {
     static const int v = [] { const char *e = DL_DEV_ENV("DL_TILE_GRID_Y"); const int n = e ? atoi(e) : 0; return (n >= 1 && n <= 65535) ? n : 32768; }();
@@ -185,6 +355,90 @@ extern "C" int dl_tile_paste_u8(int in_dtype, const void *tiles, int in_pstride,
             hipLaunchKernelGGL(tile_paste_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, (const float *)tiles, in_pstride, tile, rects + 8 * (size_t)r0, (uint8_t *)dst,
                                (long long)dst_row_stride);
         DL_CHECK_LAUNCH("dl_tile_paste_u8");
+    }
+    return 0;
+}
+
+// ---- host side of the resampled entries: strip height R and the LDS image it needs
+static int rs_ksize(int in, int out) { return 2 * (in > out ? (int)((2ll * in + out - 1) / out) : 2) + 1; }      // 2 * ceil(support) + 1, support = 2 * max(in / out, 1)
+// source rows the vertical taps of R consecutive output rows can reach: xmax(last) - xmin(first) <= (R - 1) * in / out + 2 * support + 1
+static int rs_rows_cap(int in, int out, int R) {
+    const long long r = ((long long)(R - 1) * in) / out + rs_ksize(in, out);
+    return r < in ? (int)r : in;
+}
+static size_t rs_lds_bytes(int in, int out, int R, int n_src) { return 4ull * out * ((size_t)rs_rows_cap(in, out, R) + (size_t)(n_src - 1) * R); }
+static int rs_strip_rows(int in, int out, int n_src) {
+    for (int R = out < DL_RS_MAX_STRIP ? out : DL_RS_MAX_STRIP; R >= 1; --R)
+        if (rs_lds_bytes(in, out, R, n_src) <= DL_RS_LDS_BYTES) return R;
+    return 0;
+}
+
+extern "C" int dl_tile_resample_supported(int in_size, int out_size) {
+    if (in_size <= 0 || out_size <= 0 || in_size == out_size) return 0;
+    return rs_strip_rows(in_size, out_size, DL_TILE_MAX_SRC) >= 1 ? 1 : 0;
+}
+
+extern "C" int dl_tile_gather_resample_u8(const void *const *imgs, const int64_t *row_strides, int n_src, int H0, int W0, const int32_t *origins, int n_tiles, int tile,
+                                          int pad, uint32_t pad_rgb, int net, const int32_t *bounds, const int32_t *kk, int ksize, int strip_rows, const float *lut,
+                                          int out_dtype, void *out, int out_pstride, int out_cp, void *stream) {
+    if (n_tiles <= 0 || tile <= 0 || net <= 0 || H0 <= 0 || W0 <= 0)
+        DL_FAIL("dl_tile_gather_resample_u8: empty problem (n_tiles=%d tile=%d net=%d image %dx%d)", n_tiles, tile, net, W0, H0);
+    if (tile == net) DL_FAIL("dl_tile_gather_resample_u8: tile == net == %d is dl_tile_gather_u8", net);
+    if (n_src < 1 || n_src > DL_TILE_MAX_SRC) DL_FAIL("dl_tile_gather_resample_u8: n_src=%d outside 1..%d", n_src, DL_TILE_MAX_SRC);
+    if (out_cp % 8 || out_cp < 3 * n_src || out_pstride < out_cp)
+        DL_FAIL("dl_tile_gather_resample_u8: bad channel geometry (Cp=%d pstride=%d for %d source images)", out_cp, out_pstride, n_src);
+    if (pad < 0 || 2 * pad >= tile) DL_FAIL("dl_tile_gather_resample_u8: pad=%d does not fit tile=%d", pad, tile);
+    if (!bounds || !kk || !lut) DL_FAIL("dl_tile_gather_resample_u8: the coefficient table (bounds, kk) and lut are required");
+    if (ksize != rs_ksize(tile, net)) DL_FAIL("dl_tile_gather_resample_u8: ksize=%d, the table of %d -> %d has %d", ksize, tile, net, rs_ksize(tile, net));
+    const int R = strip_rows > 0 ? (strip_rows < net ? strip_rows : net) : rs_strip_rows(tile, net, n_src);
+    if (R < 1 || rs_lds_bytes(tile, net, R, n_src) > DL_RS_LDS_BYTES)
+        DL_FAIL("dl_tile_gather_resample_u8: %d -> %d with %d source images and strips of %d rows does not fit %d bytes of LDS", tile, net, n_src, R, DL_RS_LDS_BYTES);
+    const int rows_cap = rs_rows_cap(tile, net, R);
+    const size_t lds = rs_lds_bytes(tile, net, R, n_src);
+    TileSrc s;
+    for (int i = 0; i < DL_TILE_MAX_SRC; ++i) {
+        s.img[i] = (const uint8_t *)(i < n_src ? imgs[i] : imgs[0]);
+        s.row_stride[i] = i < n_src ? row_strides[i] : row_strides[0];
+    }
+    const RsTable tb = {bounds, kk, ksize};
+    for (int t0 = 0; t0 < n_tiles; t0 += DL_TILE_GRID_Y) {
+        const int nt = n_tiles - t0 < DL_TILE_GRID_Y ? n_tiles - t0 : DL_TILE_GRID_Y;
+        dim3 grid((net + R - 1) / R, nt);
+        const size_t o0 = (size_t)t0 * net * net * out_pstride;
+        if (out_dtype == DL_BF16)
+            hipLaunchKernelGGL(tile_gather_resample_kernel<bf16_t>, grid, dim3(256), lds, (hipStream_t)stream, s, n_src, H0, W0, origins + 2 * (size_t)t0, tile, pad, pad_rgb,
+                               net, tb, R, rows_cap, lut, (bf16_t *)out + o0, out_pstride, out_cp);
+        else
+            hipLaunchKernelGGL(tile_gather_resample_kernel<float>, grid, dim3(256), lds, (hipStream_t)stream, s, n_src, H0, W0, origins + 2 * (size_t)t0, tile, pad, pad_rgb,
+                               net, tb, R, rows_cap, lut, (float *)out + o0, out_pstride, out_cp);
+        DL_CHECK_LAUNCH("dl_tile_gather_resample_u8");
+    }
+    return 0;
+}
+
+extern "C" int dl_tile_paste_resample_u8(int in_dtype, const void *tiles, int in_pstride, int net, int tile, const int32_t *bounds, const int32_t *kk, int ksize,
+                                         int strip_rows, const int32_t *rects, int n_rects, void *dst, int64_t dst_row_stride, void *stream) {
+    if (n_rects <= 0 || tile <= 0 || net <= 0) DL_FAIL("dl_tile_paste_resample_u8: empty problem (n_rects=%d tile=%d net=%d)", n_rects, tile, net);
+    if (tile == net) DL_FAIL("dl_tile_paste_resample_u8: tile == net == %d is dl_tile_paste_u8", net);
+    if (in_pstride < 8) DL_FAIL("dl_tile_paste_resample_u8: engine tiles have at least 8 padded channels (pstride=%d)", in_pstride);
+    if (!bounds || !kk || !rects || !dst) DL_FAIL("dl_tile_paste_resample_u8: the coefficient table (bounds, kk), rects and dst are required");
+    if (ksize != rs_ksize(net, tile)) DL_FAIL("dl_tile_paste_resample_u8: ksize=%d, the table of %d -> %d has %d", ksize, net, tile, rs_ksize(net, tile));
+    const int R = strip_rows > 0 ? (strip_rows < tile ? strip_rows : tile) : rs_strip_rows(net, tile, 1);
+    if (R < 1 || rs_lds_bytes(net, tile, R, 1) > DL_RS_LDS_BYTES)
+        DL_FAIL("dl_tile_paste_resample_u8: %d -> %d with strips of %d rows does not fit %d bytes of LDS", net, tile, R, DL_RS_LDS_BYTES);
+    const int rows_cap = rs_rows_cap(net, tile, R);
+    const size_t lds = rs_lds_bytes(net, tile, R, 1);
+    const RsTable tb = {bounds, kk, ksize};
+    for (int r0 = 0; r0 < n_rects; r0 += DL_TILE_GRID_Y) {
+        const int nr = n_rects - r0 < DL_TILE_GRID_Y ? n_rects - r0 : DL_TILE_GRID_Y;
+        dim3 grid((tile + R - 1) / R, nr);           // strips of a window as high as the tile; the strips past a shorter window return at once
+        if (in_dtype == DL_BF16)
+            hipLaunchKernelGGL(tile_paste_resample_kernel<bf16_t>, grid, dim3(256), lds, (hipStream_t)stream, (const bf16_t *)tiles, in_pstride, net, tile, tb, R, rows_cap,
+                               rects + 8 * (size_t)r0, (uint8_t *)dst, (long long)dst_row_stride);
+        else
+            hipLaunchKernelGGL(tile_paste_resample_kernel<float>, grid, dim3(256), lds, (hipStream_t)stream, (const float *)tiles, in_pstride, net, tile, tb, R, rows_cap,
+                               rects + 8 * (size_t)r0, (uint8_t *)dst, (long long)dst_row_stride);
+        DL_CHECK_LAUNCH("dl_tile_paste_resample_u8");
     }
     return 0;
 }

@@ -493,25 +493,36 @@ def empty_tile_colors(opt, seg_only=False, mod_only=False) -> 'OrderedDict[str, 
     return res
 
 
+def region_resample_supported(tile_size, scale) -> bool:
+    """can infer_region resample tile_size <-> scale on the GPU?  The active backend must offer the resample entries and the library must
+    hold both directions in its LDS budget (dl_tile_resample_supported); otherwise inference() keeps the host route (_inference_resampled)."""
+    be = ops.impl()
+    if not all(hasattr(be, m) for m in ('tile_gather_resampled', 'tile_paste_resampled', 'tile_resample_supported')):
+        return False
+    return bool(be.tile_resample_supported(tile_size, scale)) and bool(be.tile_resample_supported(scale, tile_size))
+
+
 def infer_region(images, tile_size, overlap_size, nets, opt, seg_only=False, mod_only=False, seg_weights=None, batch_size=8, rank=0, world=1,
                  limit_tiles=None):
     """Tile loop of inference() (deepliif/models/__init__.py:496-500) for uint8 RGB image(s) [H, W, 3] resident in HBM, entirely on
     the GPU: crop + transform (dl_tile_gather_u8), is_empty (dl_tile_gray_stats_u8), the generator DAG on batches of `batch_size`
-    tiles with per-sample normalisation, tensor2im + stitch (dl_tile_paste_u8).
+    tiles with per-sample normalisation, tensor2im + stitch (dl_tile_paste_u8).  tile_size != scale_size: the tiles are resized to the
+    networks' side and the results back with PIL's bicubic filter, bit for bit, inside the gather and the paste
+    (dl_tile_gather_resample_u8 / dl_tile_paste_resample_u8; region_resample_supported).
     Tile-parallel over `world` ranks (BASELINE configs[4]): rank r owns a contiguous band of tile rows (tiling.split_rows) and
     returns ({key: uint8 [band rows, W, 3]}, (y0, y1)); the bands of all ranks concatenate to the full result images.
     limit_tiles (measurement only): stop after that many non-empty tiles of the band."""
     from .tiling import RegionTiler, TilePlan, split_rows
     scale = _get(opt, 'scale_size', tile_size)
-    if tile_size != scale:
-        raise NotImplementedError(f'infer_region runs tiles at the network resolution (tile_size == scale_size == {scale}); '
-                                  f'inference() resamples other tile sizes with PIL on the host')
+    if tile_size != scale and not region_resample_supported(tile_size, scale):
+        raise NotImplementedError(f'infer_region runs tiles at the network resolution (tile_size == scale_size == {scale}) or resamples them on the GPU, which '
+                                  f'this backend does not offer for {tile_size} <-> {scale}; inference() resamples such tiles with PIL on the host')
     first = next(iter(nets.values()))
     prec = E.Precision.get(first.precision)
     h, w = int(images[0].shape[0]), int(images[0].shape[1])
     n_rows = len(TilePlan(w, h, tile_size, overlap_size).ys)
     with ops.half_mode(prec.half):
-        tiler = RegionTiler(images, tile_size, overlap_size, rows=split_rows(n_rows, world)[rank])
+        tiler = RegionTiler(images, tile_size, overlap_size, rows=split_rows(n_rows, world)[rank], net_size=scale)
         if len(tiler) == 0:
             return {}, tiler.band
         empty = tiler.empty_mask()
@@ -611,7 +622,8 @@ def inference(img, tile_size, overlap_size, model_path, use_torchserve=False, ea
     The tile loop runs on the GPU in batches (infer_region); `nets` / `batch_size` are extensions (default: init_nets(model_path)).
     rank / world (extension, BASELINE configs[4]): `world` ranks call this with the SAME image; each infers its band of tile rows, rank 0 gathers the
     bands (gather_bands) and returns the dict, the other ranks return None.  Everything else -- seg_gen guard, input_no / SDG split, result names --
-    is this one code path whatever the world size.  With tile_size != scale_size (PIL resampling on the host) rank 0 does the whole image."""
+    is this one code path whatever the world size.  tile_size != scale_size takes the same route (the tiles are resampled on the GPU) wherever
+    region_resample_supported says so; otherwise rank 0 does the whole image with PIL on the host (_inference_resampled)."""
     from PIL import Image
     if use_torchserve:
         raise NotImplementedError('the TorchServe client route is not part of the MI355X engine (use the in-process engine)')
@@ -632,7 +644,7 @@ def inference(img, tile_size, overlap_size, model_path, use_torchserve=False, ea
     else:
         origs = [img]
     scale = _get(opt, 'scale_size', tile_size)
-    if tile_size == scale:
+    if tile_size == scale or region_resample_supported(tile_size, scale):
         bands, band = infer_region([_to_u8_device(o, device) for o in origs], tile_size, overlap_size, nets, opt, seg_only, mod_only, seg_weights,
                                    batch_size, rank=rank, world=world)
         if world > 1:
@@ -651,8 +663,8 @@ def inference(img, tile_size, overlap_size, model_path, use_torchserve=False, ea
 
 def _inference_resampled(origs, tile_size, overlap_size, nets, opt, seg_only, mod_only, seg_weights, batch_size, scale):
     """tile_size != scale_size: the reference resamples every tile to the network resolution and every result tile back with PIL
-    (run_dask :276-280, InferenceTiler.stitch :291-292).  Resampling is image-format plumbing and stays PIL on the host; the tiles
-    still go through the generators in batches."""
+    (run_dask :276-280, InferenceTiler.stitch :291-292).  The host route: PIL on one core, rank 0 only; the tiles still go through the
+    generators in batches.  inference() takes it where region_resample_supported says no, and the GPU route is held to its bytes."""
     from PIL import Image
     from .tiling import TilePlan, gray_stats_empty
     w, h = origs[0].size

@@ -826,6 +826,39 @@ class HipBackend:
             dt, tp, ps = dl_dtype(tiles), _ptr(tiles), pstride(tiles)
         self.check(self.lib.dl_tile_paste_u8(dt, tp, ps, tile, _ptr(rects), rects.shape[0], _ptr(dst), dst.stride(0), _stream(dst)), 'dl_tile_paste_u8')
 
+    # ---- resampled tiles (tile_size != scale_size): PIL's bicubic resize between the crop and the network, and between the network and the paste;
+    # table = (bounds, kk) device int32 tensors of tiling.resample_table(in, out); strip_rows 0 = the library's choice
+    def tile_resample_supported(self, in_size, out_size):
+        return bool(self.lib.dl_tile_resample_supported(int(in_size), int(out_size)))
+
+    def tile_gather_resampled(self, images, H0, W0, origins, tile, pad, pad_rgb, net, table, lut, out, strip_rows=0):
+        bounds, kk = table
+        _need_cuda(origins, lut, out, bounds, kk, *images)
+        assert origins.dtype == torch.int32 and origins.is_contiguous() and lut.dtype == torch.float32 and lut.numel() == 256
+        assert bounds.dtype == torch.int32 and kk.dtype == torch.int32 and bounds.is_contiguous() and kk.is_contiguous()
+        assert tuple(bounds.shape) == (net, 2) and kk.shape[0] == net and tuple(out.shape[:3]) == (origins.shape[0], net, net)
+        n = len(images)
+        ptrs = (C.c_void_p * n)(*[im.data_ptr() for im in images])
+        strides = (C.c_int64 * n)(*[im.stride(0) for im in images])
+        self.check(self.lib.dl_tile_gather_resample_u8(ptrs, strides, n, H0, W0, _ptr(origins), origins.shape[0], tile, pad, pad_rgb, net, _ptr(bounds), _ptr(kk),
+                                                    kk.shape[1], strip_rows, _ptr(lut), dl_dtype(out), _ptr(out), pstride(out), out.shape[3], _stream(out)),
+                   'dl_tile_gather_resample_u8')
+
+    def tile_paste_resampled(self, tiles, net, tile, table, rects, dst, strip_rows=0):
+        bounds, kk = table
+        _need_cuda(tiles, rects, dst, bounds, kk)
+        assert rects.dtype == torch.int32 and rects.is_contiguous() and rects.shape[1] == 8
+        assert dst.dtype == torch.uint8 and dst.stride(2) == 1 and dst.stride(1) == 3
+        assert bounds.dtype == torch.int32 and kk.dtype == torch.int32 and bounds.is_contiguous() and kk.is_contiguous()
+        assert tuple(bounds.shape) == (tile, 2) and kk.shape[0] == tile
+        if tiles is None:
+            dt, tp, ps = L.DL_F32, None, 8
+        else:
+            assert tuple(tiles.shape[1:3]) == (net, net)
+            dt, tp, ps = dl_dtype(tiles), _ptr(tiles), pstride(tiles)
+        self.check(self.lib.dl_tile_paste_resample_u8(dt, tp, ps, net, tile, _ptr(bounds), _ptr(kk), kk.shape[1], strip_rows, _ptr(rects), rects.shape[0], _ptr(dst),
+                                                   dst.stride(0), _stream(dst)), 'dl_tile_paste_resample_u8')
+
     # ---- losses
     def loss(self, kind, x, target, target_const, C_real, loss_out, grad, grad_scale, out_scale=1.0, accumulate=False):
         """loss_out[0] = (accumulate ? loss_out[0] : 0) + out_scale * mean loss; grad = grad_scale * d(mean loss)/dx"""

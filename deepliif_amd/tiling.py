@@ -14,9 +14,14 @@ computed up front, in closed form:
 TilePlan holds that geometry (pinned against the reference's own iteration and paste sequence through the oracle,
 tests/test_tiling_host.py).  RegionTiler runs it on a uint8 RGB image resident in HBM: dl_tile_gather_u8 (crop + transform()),
 dl_tile_gray_stats_u8 (is_empty), dl_tile_paste_u8 (tensor2im + stitch) -- include/deepliif_hip.h.
+
+tile_size != the networks' side (a slide scanned at 20x or 10x): the reference resizes every tile up and every result tile down with
+PIL.  resample_table() restates Pillow's integer bicubic coefficients; dl_tile_gather_resample_u8 / dl_tile_paste_resample_u8 apply
+them on the GPU, so RegionTiler(net_size=...) serves that case with the same geometry and the same bytes.
 """
 from __future__ import annotations
 
+import math
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -109,6 +114,80 @@ def transform_lut() -> np.ndarray:
     return ((v - np.float32(0.5)) / np.float32(0.5)).astype(np.float32)
 
 
+RESAMPLE_PRECISION_BITS = 22          # Pillow's fixed point for 8-bit images (32 - 8 - 2)
+_RESAMPLE_TABLES: Dict[Tuple[int, int], Tuple[np.ndarray, np.ndarray]] = {}
+
+
+def _bicubic(x: float) -> float:
+    """Pillow's bicubic kernel (a = -0.5), operation for operation"""
+    a = -0.5
+    if x < 0.0:
+        x = -x
+    if x < 1.0:
+        return ((a + 2.0) * x - (a + 3.0)) * x * x + 1
+    if x < 2.0:
+        return (((x - 5) * x + 8) * x - 4) * a
+    return 0.0
+
+
+def resample_table(in_size: int, out_size: int) -> Tuple[np.ndarray, np.ndarray]:
+    """Integer coefficient table of PIL's Image.resize (default bicubic, 8-bit) along one axis, in_size -> out_size pixels:
+    (bounds int32 [out_size, 2] = (xmin, n), kk int32 [out_size, ksize] zero-filled past n, ksize = 2 * ceil(support) + 1).
+    Output byte xx = clip((2**21 + sum_k pixel[xmin + k] * kk[xx, k]) >> 22, 0, 255) with a 32-bit accumulator; a resize runs the
+    horizontal pass first, writes uint8, and the vertical pass reads those bytes.  Python floats are IEEE doubles and the operations
+    below keep Pillow's order (the filter argument is scaled by the reciprocal 1 / filterscale, as Pillow does), so the table holds
+    Pillow's bits; the device kernels (dl_tile_gather_resample_u8 / dl_tile_paste_resample_u8) only apply it.  Cached per pair."""
+    key = (int(in_size), int(out_size))
+    if key not in _RESAMPLE_TABLES:
+        n_in, n_out = key
+        if n_in <= 0 or n_out <= 0:
+            raise ValueError('resample_table sizes must be positive')
+        scale = n_in / n_out
+        filterscale = scale if scale > 1.0 else 1.0
+        support = 2.0 * filterscale
+        ksize = 2 * int(math.ceil(support)) + 1
+        ss = 1.0 / filterscale
+        one = float(1 << RESAMPLE_PRECISION_BITS)
+        bounds = np.zeros((n_out, 2), dtype=np.int32)
+        kk = np.zeros((n_out, ksize), dtype=np.int32)
+        for xx in range(n_out):
+            center = (xx + 0.5) * scale
+            xmin = max(int(center - support + 0.5), 0)
+            xmax = min(int(center + support + 0.5), n_in)
+            n = xmax - xmin
+            w = [_bicubic((x + xmin - center + 0.5) * ss) for x in range(n)]
+            ww = 0.0
+            for v in w:                       # left to right, in double
+                ww += v
+            if ww != 0.0:
+                w = [v / ww for v in w]
+            bounds[xx] = (xmin, n)
+            kk[xx, :n] = [int(-0.5 + v * one) if v < 0 else int(0.5 + v * one) for v in w]
+        bounds.setflags(write=False)
+        kk.setflags(write=False)
+        _RESAMPLE_TABLES[key] = (bounds, kk)
+    return _RESAMPLE_TABLES[key]
+
+
+def resample_apply(a: np.ndarray, out_size: int) -> np.ndarray:
+    """resample_table() applied in numpy to a square uint8 image [S, S, C] -> [out_size, out_size, C]: what the device kernels
+    compute and what Image.resize returns (the tests hold all three to equality)"""
+    def one_pass(src, axis_len_out):
+        bounds, kk = resample_table(src.shape[1], axis_len_out)
+        acc = np.full((src.shape[0], axis_len_out, src.shape[2]), 1 << (RESAMPLE_PRECISION_BITS - 1), dtype=np.int32)
+        s32 = src.astype(np.int32)
+        for xx in range(axis_len_out):
+            x0, n = (int(v) for v in bounds[xx])
+            acc[:, xx] += (s32[:, x0:x0 + n] * kk[xx, :n, None]).sum(axis=1, dtype=np.int32)
+        return np.clip(acc >> RESAMPLE_PRECISION_BITS, 0, 255).astype(np.uint8)
+    if a.shape[0] != a.shape[1]:
+        raise ValueError('resample_apply takes square tiles')
+    if a.shape[1] != out_size:
+        a = one_pass(a, out_size)                                            # horizontal
+        a = one_pass(a.transpose(1, 0, 2), out_size).transpose(1, 0, 2)      # vertical, on the uint8 intermediate
+    return np.ascontiguousarray(a)
+
+
 def gray_stats_empty(stats: np.ndarray) -> np.ndarray:
     """is_empty from {count, sum, sumsq} rows (exact): variance < 9 <=> n*s2 - s1^2 < 9*n^2; no pixel in 1..254 -> variance 0"""
     n, s1, s2 = (stats[:, k].astype(object) for k in range(3))         # Python ints: no overflow whatever the tile size
@@ -124,10 +203,15 @@ class RegionTiler:
 
     `rows=(j0, j1)` restricts the tiler to the tile rows j0..j1-1 of the plan: the rectangles those tiles own form ONE contiguous
     horizontal band of the result, so tile-parallel inference over R ranks is "every rank takes a band, the bands are concatenated"
-    -- no overlap to resolve, no collective on the data path (BASELINE configs[4]; deepliif_amd.inference.infer_region)."""
+    -- no overlap to resolve, no collective on the data path (BASELINE configs[4]; deepliif_amd.inference.infer_region).
+
+    `net_size` (when it differs from tile_size): the side the networks run at.  gather() then resizes every tile to it and paste()
+    takes [n, net, net, cp] activations and resizes them back, both with PIL's bicubic filter bit for bit (resample_table,
+    dl_tile_gather_resample_u8 / dl_tile_paste_resample_u8).  The geometry -- plan, rectangles, bands, results() -- and empty_mask()
+    stay in tile coordinates: the reference tests the un-resized tile (run_wrapper, models/__init__.py:399-405)."""
 
     def __init__(self, images: Sequence[torch.Tensor], tile_size: int, overlap_size: int = 0, pad_size: int = 0, pad_color=(255, 255, 255),
-                 rows: Optional[Tuple[int, int]] = None):
+                 rows: Optional[Tuple[int, int]] = None, net_size: Optional[int] = None):
         assert images, 'at least one image'
         for im in images:
             if im.dtype != torch.uint8 or im.dim() != 3 or im.shape[2] != 3 or im.stride(2) != 1 or im.stride(1) != 3:
@@ -150,6 +234,11 @@ class RegionTiler:
         self.lut = torch.from_numpy(transform_lut()).to(self.device)
         self._rects = p.paste_rects()
         self._results: Dict[str, torch.Tensor] = {}
+        self.net_size = int(net_size) if net_size is not None and int(net_size) != p.tile_size else None
+        if self.net_size is not None:
+            dev = lambda tb: tuple(torch.from_numpy(np.array(a)).to(self.device) for a in tb)
+            self._table_in = dev(resample_table(p.tile_size, self.net_size))        # tile -> net, before the networks
+            self._table_out = dev(resample_table(self.net_size, p.tile_size))       # net -> tile, after them
 
     def __len__(self):
         return len(self.tile_ids)
@@ -173,8 +262,14 @@ class RegionTiler:
         return empty
 
     def gather(self, tile_ids: Sequence[int], dtype: torch.dtype, cp: int) -> torch.Tensor:
-        """engine tile batch [len(tile_ids), tile, tile, cp] in [-1, 1] (crop + transform)"""
+        """engine tile batch [len(tile_ids), tile, tile, cp] in [-1, 1] (crop + transform); with net_size: [len(tile_ids), net, net, cp]
+        (crop + resize + transform)"""
         p = self.plan
+        if self.net_size is not None:
+            out = torch.empty((len(tile_ids), self.net_size, self.net_size, cp), dtype=dtype, device=self.device)
+            ops.impl().tile_gather_resampled(self.images, p.orig_height, p.orig_width, self._origins_of(tile_ids), p.tile_size, p.pad_size, self.pad_rgb,
+                                             self.net_size, self._table_in, self.lut, out)
+            return out
         out = torch.empty((len(tile_ids), p.tile_size, p.tile_size, cp), dtype=dtype, device=self.device)
         ops.impl().tile_gather(self.images, p.orig_height, p.orig_width, self._origins_of(tile_ids), p.tile_size, p.pad_size, self.pad_rgb, self.lut, out)
         return out
@@ -190,7 +285,7 @@ class RegionTiler:
 
     def paste(self, key: str, tiles: Optional[torch.Tensor], tile_ids: Sequence[int], const_rgb=None):
         """stitch tiles[i] (engine layout, values in [-1, 1]) as tile tile_ids[i] of result image `key`; tiles None pastes the
-        constant colour instead (empty tiles)."""
+        constant colour instead (empty tiles).  With net_size the tiles are [n, net, net, cp] and are resized to the tile first."""
         if not len(tile_ids):
             return
         p = self.plan
@@ -200,8 +295,13 @@ class RegionTiler:
         rec[:, 6] -= p._iy[self.rows[0]][0]                            # band-local row
         rec[:, 7] = 0 if const_rgb is None else _rgb_word(const_rgb)
         rec = rec[(rec[:, 3] > 0) & (rec[:, 4] > 0)]
-        if len(rec):
-            ops.impl().tile_paste(tiles, p.tile_size, torch.from_numpy(np.ascontiguousarray(rec)).to(self.device), self.result(key))
+        if not len(rec):
+            return
+        rects = torch.from_numpy(np.ascontiguousarray(rec)).to(self.device)
+        if self.net_size is not None and tiles is not None:
+            ops.impl().tile_paste_resampled(tiles, self.net_size, p.tile_size, self._table_out, rects, self.result(key))
+        else:
+            ops.impl().tile_paste(tiles, p.tile_size, rects, self.result(key))
 
     def results(self) -> Dict[str, torch.Tensor]:
         """result bands cropped back to the original image (util/__init__.py:322-331): rows band[0]..band[1] of the full result"""

@@ -136,7 +136,9 @@ def infer_slide(read_region: Callable[[int, int, int, int], 'object'], size_x: i
                 on_region(job.xywh, images, scoring)
             continue
         # bands: every rank infers its tile rows of this region; rank 0 reassembles and post-processes -- through the SAME infer_modalities() as the
-        # 'regions' mode (scale_size resampling, input_no / SDG split, seg_gen guard and the seg_only clean-up do not depend on the world size)
+        # 'regions' mode (input_no / SDG split, seg_gen guard and the seg_only clean-up do not depend on the world size; with tile_size != scale_size
+        # every rank resamples and infers its own band on the GPU, and only where inference.region_resample_supported says no does rank 0 do the whole
+        # region through PIL on the host)
         import torch
         if torch.is_tensor(region):
             region = region.cpu().numpy()

@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define DL_VERSION 115
+#define DL_VERSION 116
 
 enum { DL_F32 = 0, DL_BF16 = 1 };           /* DL_BF16 = "the 16-bit type of this library": bfloat16, or IEEE half in libdeepliif_hip_f16.so (below) */
 enum { DL_HALF_BF16 = 0, DL_HALF_FP16 = 1 };   /* dl_half_format() */
@@ -456,6 +456,25 @@ int dl_adam_step_dev(float *param, const float *grad, float *exp_avg, float *exp
  *                         result image; slot < 0 pastes the constant colour rgb (r | g<<8 | b<<16) instead (empty tiles,
  *                         deepliif/models/__init__.py:399-440).  The caller resolves overlapping pastes (last writer wins) into
  *                         disjoint rectangles, so the launch is order-independent.
+ *
+ * Resampled tiles (tile_size != scale_size: the reference resizes every tile to the network's side with PIL, run_dask
+ * deepliif/models/__init__.py:276-280, and every result tile back, InferenceTiler.stitch util/__init__.py:289-290).  PIL's
+ * Image.resize of an 8-bit image is a separable bicubic filter in integer arithmetic; the caller supplies its coefficient table for
+ * one axis, in -> out pixels (tiles are square: one table serves both axes; deepliif_amd/tiling.py resample_table computes it in
+ * doubles in Pillow's order -- the library computes no coefficient, so no compiler flag can change a table bit):
+ *     bounds  device int32 [out][2] = {xmin, n}: output coordinate xx reads the n source pixels xmin .. xmin + n - 1
+ *     kk      device int32 [out][ksize], 22-bit fixed point, zero past n; ksize = 2 * ceil(2 * max(in / out, 1)) + 1
+ *     byte    = clip((2^21 + sum_k pixel[xmin + k] * kk[xx][k]) >> 22, 0, 255), 32-bit signed accumulator
+ * The horizontal pass runs first and writes uint8; the vertical pass reads those bytes.  One workgroup owns one tile and a strip of R
+ * output rows; the horizontally resized source rows its vertical taps need live in LDS (4 bytes per pixel), never in HBM.
+ * strip_rows = 0 lets the library choose R (the largest up to 32 whose LDS image fits 64 KB); a positive value is used as given and
+ * fails if it does not fit.
+ *   dl_tile_resample_supported   1 when in_size -> out_size fits that budget with R = 1 for DL_TILE_MAX_SRC source images (every
+ *                                ratio up to about 7 : 1 at width 512), else 0 (also for in_size == out_size: nothing to resample).
+ *   dl_tile_gather_resample_u8   dl_tile_gather_u8 with the resize tile -> net between the crop and lut[]: engine tile batch
+ *                                [n_tiles][net][net][Cp].  The table is that of resample_table(tile, net).
+ *   dl_tile_paste_resample_u8    dl_tile_paste_u8 for engine tiles [n][net][net][Cp]: tensor2im, resize net -> tile (the table of
+ *                                resample_table(net, tile)), then the rectangle records, which stay in TILE coordinates.
  * ---------------------------------------------------------------------------------------------------------- */
 #define DL_TILE_MAX_SRC 4
 int dl_tile_gather_u8(const void *const *imgs /*host array of device pointers*/, const int64_t *row_strides /*host*/, int n_src, int H0, int W0,
@@ -465,6 +484,13 @@ int dl_tile_gray_stats_u8(const void *img, int64_t row_stride, int H0, int W0, c
                           uint32_t pad_rgb, uint64_t *stats, void *stream);
 int dl_tile_paste_u8(int in_dtype, const void *tiles, int in_pstride, int tile, const int32_t *rects, int n_rects, void *dst,
                      int64_t dst_row_stride, void *stream);
+int dl_tile_resample_supported(int in_size, int out_size);
+int dl_tile_gather_resample_u8(const void *const *imgs /*host array of device pointers*/, const int64_t *row_strides /*host*/, int n_src, int H0, int W0,
+                               const int32_t *origins, int n_tiles, int tile, int pad, uint32_t pad_rgb, int net, const int32_t *bounds,
+                               const int32_t *kk, int ksize, int strip_rows, const float *lut, int out_dtype, void *out, int out_pstride, int out_cp,
+                               void *stream);
+int dl_tile_paste_resample_u8(int in_dtype, const void *tiles, int in_pstride, int net, int tile, const int32_t *bounds, const int32_t *kk, int ksize,
+                              int strip_rows, const int32_t *rects, int n_rects, void *dst, int64_t dst_row_stride, void *stream);
 
 /* hardware probes used by the GPU test-suite (MFMA fragment layouts, ds_read_b64_tr_b16 semantics) */
 int dl_probe_mfma16(const uint16_t *a /*16x32 bf16 row-major*/, const uint16_t *b /*32x16*/, float *d /*16x16*/, void *stream);
