@@ -28,10 +28,15 @@ static NormGeom make_geom_fwd(const dl_norm_desc *d) {
     return g;
 }
 
+// Rows of Cp floats the workspace reserves for the per-block channel sums of dy (norm_bwd_apply_kernel writes row n * gridDim.x + blockIdx.x).
+// apply_grid never launches more than this many blocks over the whole batch -- or N of them when N alone is larger: the region covers max(this, N) rows.
+constexpr int kBiasPartRows = 2048;
+
 extern "C" size_t dl_norm_ws_floats(const dl_norm_desc *d) {
     NormGeom g = make_geom(d);
     if (d->ext_nchunks > g.nchunks) g.nchunks = d->ext_nchunks;
-    return (size_t)g.N * g.nchunks * 2 * g.Cp + (size_t)4 * g.N * g.Cp + (size_t)2048 * g.Cp + 64;    // partials | chunk sums | c1 | c2 | dy channel-sum partials
+    const size_t brows = g.N > kBiasPartRows ? (size_t)g.N : (size_t)kBiasPartRows;
+    return (size_t)g.N * g.nchunks * 2 * g.Cp + (size_t)4 * g.N * g.Cp + brows * g.Cp + 64;    // partials | chunk sums | c1 | c2 | dy channel-sum partials
 }
 
 // Non-temporal accesses (compile-time knob; round-6 A/B of six settings under rocprofv3, tools/gpu_r06_nt.sh, profiles/r06/norm_nt_r06.txt):
@@ -435,9 +440,12 @@ static dim3 apply_grid(const NormGeom &g) {
     const int cvec = g.Cp / 8;
     const int rows = 256 / (cvec < 256 ? cvec : 256);
     int bx = (g.HW + rows * 16 - 1) / (rows * 16);
-    // A/B switch for the open launch-shape question (profiles/r01/pmc_norm/README.txt): DL_NORM_GRID_MUL scales the block count
+    // A/B switch for the open launch-shape question (profiles/r01/pmc_norm/README.txt): DL_NORM_GRID_MUL scales the block count (below 1 only: the cap binds above)
     static const float mul = [] { const char *e = DL_DEV_ENV("DL_NORM_GRID_MUL"); const float v = e ? (float)atof(e) : 1.f; return v > 0.f ? v : 1.f; }();
-    const int want = (int)((2048 * mul + g.N - 1) / g.N);
+    // rounded DOWN and clamped after the multiplier: bx * N rows of bias partials must fit the kBiasPartRows (or N) rows dl_norm_ws_floats reserves
+    const int cap = kBiasPartRows / g.N > 1 ? kBiasPartRows / g.N : 1;
+    int want = (int)(cap * mul);
+    if (want > cap) want = cap;
     if (bx > want) bx = want;
     if (bx < 1) bx = 1;
     return dim3(bx, g.N);
