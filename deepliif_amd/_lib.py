@@ -15,12 +15,13 @@ HALF_BF16, HALF_FP16 = 0, 1
 DL_F32, DL_BF16 = 0, 1
 PREC_BF16, PREC_BF16X3 = 1, 3
 ACT_NONE, ACT_RELU, ACT_LRELU, ACT_TANH, ACT_SIGMOID = 0, 1, 2, 3, 4
-PAD_ZERO, PAD_REFLECT = 0, 1
+PAD_ZERO, PAD_REFLECT, PAD_REPLICATE = 0, 1, 2
+FOLD_SRC_F32 = 0x100        # dl_replicate_fold: dtype | FOLD_SRC_F32 = fp32 source (raw accumulators), 16-bit destination
 NORM_INSTANCE, NORM_BATCH = 0, 1
 LOSS_BCE_LOGITS, LOSS_MSE, LOSS_SMOOTH_L1, LOSS_L1, LOSS_LINEAR = 0, 1, 2, 3, 4
 MAX_TAPS, MAX_PHASES = 64, 4
 WGRAD_MULTI_MAX = 24
-DL_VERSION = 116
+DL_VERSION = 117
 
 i32 = C.c_int32
 
@@ -128,6 +129,7 @@ SIGNATURES = {
     'dl_shift_sum': (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _i, _vp, _i, _i, _vp]),
     'dl_shift_stack': (_i, [_i, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _vp]),
     'dl_reflect_fold': (_i, [_i, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    'dl_replicate_fold': (_i, [_i, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     'dl_loss_ws_floats': (C.c_size_t, []),
     'dl_loss': (_i, [_i, _i, _vp, _i, _vp, _i, _f, _i64, _i, _i, _vp, _vp, _i, _f, _vp, _vp]),
     'dl_loss_acc': (_i, [_i, _i, _vp, _i, _vp, _i, _f, _i64, _i, _i, _vp, _f, _i, _vp, _i, _f, _vp, _vp]),

@@ -240,6 +240,13 @@ __device__ __forceinline__ int xcd_remap(int bid, int nwg) {
     return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
 }
 
+// Border map of the non-zero padding modes: the source index that padded position i (-pad <= i < n + pad) of an axis of length n copies.
+// DL_PAD_REPLICATE clamps to the edge (nn.ReplicationPad2d), DL_PAD_REFLECT mirrors without repeating it (nn.ReflectionPad2d, pad < n).  Zero padding
+// has no source pixel: callers test the bounds instead and never get here.
+__host__ __device__ constexpr int border_idx(int mode, int i, int n) {
+    return mode == DL_PAD_REPLICATE ? (i < 0 ? 0 : (i >= n ? n - 1 : i)) : ((i < 0 ? -i : i) >= n ? 2 * n - 2 - (i < 0 ? -i : i) : (i < 0 ? -i : i));
+}
+
 // ---- runtime switches (include/deepliif_hip.h, "Runtime switches").  The shipped library looks at NINE documented environment variables, all of them
 // choices between two correct code paths, read ONCE when the library is loaded (error.cpp; dl_switches_reload() re-reads them for tests): no getenv on a
 // launch path, nothing that changes while threads are launching.  Everything else -- kernel variants kept for A/B measurements and the timing-only

@@ -95,7 +95,7 @@ __global__ void __launch_bounds__(256, 2) conv_c4_patch_kernel(const C4Args ca) 
             const int i = tid + k * 256;
             const int pr = i / (TC + KR), pc = i - pr * (TC + KR);
             int hi = th * TR - 3 + pr, wi = tw * TC - 3 + pc;
-            if (PADMODE == DL_PAD_REFLECT) { hi = reflect_idx(hi, a.Hi); wi = reflect_idx(wi, a.Wi); }
+            if (PADMODE != DL_PAD_ZERO) { hi = border_idx(PADMODE, hi, a.Hi); wi = border_idx(PADMODE, wi, a.Wi); }
             const bool ok = i < PR * (TC + KR) && (unsigned)hi < (unsigned)a.Hi && (unsigned)wi < (unsigned)a.Wi;
             u32x2_t v = {0u, 0u};
             if (ok) v = *reinterpret_cast<const u32x2_t *>(in + ((size_t)(n * a.Hi + hi) * a.Wi + wi) * 8);
@@ -253,13 +253,13 @@ static void c4_fill_args(C4Args &ca, const ConvArgs &a0, const dl_conv_desc *d) 
 
 // launch with the dynamic-LDS attribute set once per instantiation
 static int c4_launch(void (*kern)(const C4Args), const C4Args &ca, const dl_conv_desc *d, size_t smem, hipStream_t stream, const char *what) {
-    static void (*attr_done[12])(const C4Args) = {};
+    static void (*attr_done[18])(const C4Args) = {};
     bool seen = false;
-    for (int i = 0; i < 12; ++i) seen |= attr_done[i] == kern;
+    for (int i = 0; i < 18; ++i) seen |= attr_done[i] == kern;
     if (!seen) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
         if (e != hipSuccess) DL_FAIL("%s: hipFuncSetAttribute(%zu): %s", what, smem, hipGetErrorString(e));
-        for (int i = 0; i < 12; ++i)
+        for (int i = 0; i < 18; ++i)
             if (!attr_done[i]) { attr_done[i] = kern; break; }
     }
     const int ntiles = d->N * ca.tiles_w * ca.tiles_h;
@@ -275,11 +275,13 @@ static int launch_conv_c4(const ConvArgs &a0, const dl_conv_desc *d, hipStream_t
     c4_fill_args(ca, a0, d);
     constexpr size_t smem = 4 * 64 * 64 * 2 + 4 * 64 * sizeof(float);          // output tile (aliases the two patch copies) + statistics
     void (*kern)(const C4Args) = nullptr;
-    const bool refl = d->pad_mode == DL_PAD_REFLECT;
+    // one instantiation per (border, activation): d->pad_mode was validated by dl_conv_forward (0 .. 2)
+#define DL_C4_PICK(ACT) (d->pad_mode == DL_PAD_REFLECT ? conv_c4_patch_kernel<DL_PAD_REFLECT, ACT> : (d->pad_mode == DL_PAD_REPLICATE ? conv_c4_patch_kernel<DL_PAD_REPLICATE, ACT> : conv_c4_patch_kernel<DL_PAD_ZERO, ACT>))
     switch (d->act) {
-        case DL_ACT_RELU: kern = refl ? conv_c4_patch_kernel<DL_PAD_REFLECT, DL_ACT_RELU> : conv_c4_patch_kernel<DL_PAD_ZERO, DL_ACT_RELU>; break;
-        case DL_ACT_LRELU: kern = refl ? conv_c4_patch_kernel<DL_PAD_REFLECT, DL_ACT_LRELU> : conv_c4_patch_kernel<DL_PAD_ZERO, DL_ACT_LRELU>; break;
-        default: kern = refl ? conv_c4_patch_kernel<DL_PAD_REFLECT, DL_ACT_NONE> : conv_c4_patch_kernel<DL_PAD_ZERO, DL_ACT_NONE>; break;
+        case DL_ACT_RELU: kern = DL_C4_PICK(DL_ACT_RELU); break;
+        case DL_ACT_LRELU: kern = DL_C4_PICK(DL_ACT_LRELU); break;
+        default: kern = DL_C4_PICK(DL_ACT_NONE); break;
     }
+#undef DL_C4_PICK
     return c4_launch(kern, ca, d, smem, stream, "dl_conv_forward(c4 patch)");
 }

@@ -41,11 +41,6 @@ int launch_conv_s2d(const ConvArgs &a0, hipStream_t stream);
 bool s2f_x3_eligible(const ConvArgs &a);
 int launch_conv_s2f_x3(const ConvArgs &a0, hipStream_t stream);
 
-__device__ __forceinline__ int reflect_idx(int i, int n) {
-    i = i < 0 ? -i : i;
-    return i >= n ? 2 * n - 2 - i : i;
-}
-
 // raw staging registers for one 8-element chunk
 template <typename T> struct Raw8;
 template <> struct Raw8<bf16_t> { u32x4_t v; };
@@ -161,9 +156,9 @@ __global__ void __launch_bounds__(256) conv_gemm_kernel(const ConvArgs a) {
         for (int i = 0; i < X_CH; ++i) {
             int hi = x_hi0[i] + dh, wi = x_wi0[i] + dw;
             bool ok = x_ok[i] && tap_ok;
-            if (a.pad_mode == DL_PAD_REFLECT) {
-                hi = reflect_idx(hi, a.Hi);
-                wi = reflect_idx(wi, a.Wi);
+            if (a.pad_mode != DL_PAD_ZERO) {
+                hi = border_idx(a.pad_mode, hi, a.Hi);
+                wi = border_idx(a.pad_mode, wi, a.Wi);
             } else {
                 ok = ok && ((unsigned)hi < (unsigned)a.Hi) && ((unsigned)wi < (unsigned)a.Wi);
             }
@@ -693,7 +688,7 @@ __global__ void __launch_bounds__(WM * WN * 64) conv_gemm_glds_kernel(const Conv
             for (int t = 0; t < ntaps; ++t) {
                 const int16_t tp = a.taps[tap0 + t];
                 const int hi = x_hi0[i] + (int)(int8_t)(tp & 0xff), wi = x_wi0[i] + (int)(int8_t)((tp >> 8) & 0xff);
-                if (a.pad_mode == DL_PAD_REFLECT || (((unsigned)hi < (unsigned)a.Hi) && ((unsigned)wi < (unsigned)a.Wi))) mk |= 1ull << t;
+                if (a.pad_mode != DL_PAD_ZERO || (((unsigned)hi < (unsigned)a.Hi) && ((unsigned)wi < (unsigned)a.Wi))) mk |= 1ull << t;
             }
         }
         x_mask[i] = mk;
@@ -746,7 +741,7 @@ __global__ void __launch_bounds__(WM * WN * 64) conv_gemm_glds_kernel(const Conv
                     const int16_t t = tap_lds[tap0 + tli];
                     const int dh = (int)(int8_t)(t & 0xff), dw = (int)(int8_t)((t >> 8) & 0xff);
                     int hi = x_hi0[i] + dh, wi = x_wi0[i] + dw;
-                    if (a.pad_mode == DL_PAD_REFLECT) { hi = reflect_idx(hi, a.Hi); wi = reflect_idx(wi, a.Wi); }
+                    if (a.pad_mode != DL_PAD_ZERO) { hi = border_idx(a.pad_mode, hi, a.Hi); wi = border_idx(a.pad_mode, wi, a.Wi); }
                     const bool ok = x_ok[i] && (tl < ntaps) && ((unsigned)hi < (unsigned)a.Hi) && ((unsigned)wi < (unsigned)a.Wi);
                     const ptrdiff_t off = ((ptrdiff_t)(hi - x_hi0[i]) * a.Wi + (wi - x_wi0[i])) * (ptrdiff_t)a.in_pstride + ci - x_chunk[i] * 8;
                     const bf16_t *src = ok ? x_ptr[i] + off : zero;
@@ -1548,9 +1543,14 @@ static bool w4_enabled() {
     return !(w4 && w4[0] == '0');
 }
 
+// A replicate-padded ResnetBlock conv takes conv_gemm_w4_kernel at ANY tile count: its alternative is not the 8-phase kernel but the per-chunk
+// gather (a non-zero border never reaches the scalar-tap kernels), and one routing rule per mode keeps small and large launches of a layer on one kernel.
+static bool w4_takes_replicate(const ConvArgs &a) { return a.pad_mode == DL_PAD_REPLICATE && w4_enabled() && w4_eligible(a); }
+
 static int dispatch_tile_glds(const ConvArgs &a, hipStream_t stream) {
     if (a.Co <= 16) return launch_conv_glds<256, 16, 32, 4, 1>(a, stream);
     if (a.Co <= 64) return launch_conv_glds<128, 64, 64, 2, 2>(a, stream);
+    if (w4_takes_replicate(a)) return launch_conv_w4(a, stream);
     static const bool no_big = DL_DEV_ENV("DL_NO_BIGTILE") != nullptr;
     // 256x256x64, 8 waves (each 128 pixels x 64 channels): twice the FLOP per staged byte of the 128x128 tile; needs
     // enough tiles to fill 256 CUs
@@ -1768,6 +1768,12 @@ static int glds_tile_bm(const dl_conv_desc *d) {
     static const bool no_big = DL_DEV_ENV("DL_NO_BIGTILE") != nullptr;
     const int mtot = d->N * d->Hq * d->Wq;
     if (!no_big && big_tile_fills_gpu(mtot, d->Co, d->n_phase, d->splitk)) return 256;
+    if (d->pad_mode == DL_PAD_REPLICATE) {
+        ConvArgs a;
+        memset(&a, 0, sizeof(a));
+        fill_conv_geometry(a, d);
+        if (w4_takes_replicate(a)) return 256;
+    }
     return 128;
 }
 
@@ -1893,7 +1899,8 @@ extern "C" int dl_conv_forward(const dl_conv_desc *d, const void *in, const void
 // epilogue -- today conv_gemm_w4_kernel, the ResnetBlock shape, where the data gradient of the block's first conv meets the gradient that came down the skip
 // connection (networks.py:509-513: out = x + conv_block(x)).  `addend` may be `out` itself (every thread reads its 16 bytes before it writes them).
 extern "C" int dl_conv_add_supported(const dl_conv_desc *d) {
-    return d && d->splitk == 1 && !d->raw_out && strcmp(dl_conv_kernel_name(d), "conv_gemm_w4_kernel") == 0;
+    // (zero padding only: the data gradient of a reflect / replicate layer is the pad-0 plan over the padded extent + a fold, nothing to add to in place)
+    return d && d->splitk == 1 && !d->raw_out && d->pad_mode == DL_PAD_ZERO && strcmp(dl_conv_kernel_name(d), "conv_gemm_w4_kernel") == 0;
 }
 
 extern "C" int dl_conv_forward_add(const dl_conv_desc *d, const void *in, const void *w_hi, const void *w_lo, const void *addend, int32_t addend_pstride,
@@ -1935,7 +1942,10 @@ static int conv_forward_impl(const dl_conv_desc *d, const void *in, const void *
     if (d->in_dtype != d->out_dtype) DL_FAIL("dl_conv_forward: in/out dtype must match");
     if (d->splitk < 1 || ((d->splitk > 1 || d->raw_out) && !slab)) DL_FAIL("dl_conv_forward: splitk=%d / raw_out needs a slab", d->splitk);
     if (d->raw_out && d->splitk != 1) DL_FAIL("dl_conv_forward: raw_out requires splitk == 1");
+    if (d->pad_mode < DL_PAD_ZERO || d->pad_mode > DL_PAD_REPLICATE) DL_FAIL("dl_conv_forward: pad_mode=%d (0 zero | 1 reflect | 2 replicate)", d->pad_mode);
     if (d->pad_mode == DL_PAD_REFLECT && (d->n_phase != 1)) DL_FAIL("dl_conv_forward: reflect padding only for single-phase layers");
+    if (d->pad_mode == DL_PAD_REPLICATE && (d->n_phase != 1 || d->in_step != 1))
+        DL_FAIL("dl_conv_forward: replicate padding only for single-phase, in_step == 1 layers (n_phase=%d, in_step=%d)", d->n_phase, d->in_step);
     if ((size_t)d->N * d->Hi * d->Wi * (size_t)d->in_pstride >= ((size_t)1 << 40)) DL_FAIL("dl_conv_forward: tensor too large");
     for (int p = 0; p < d->n_phase; ++p)
         if (d->phase_kbase[p] % 64) DL_FAIL("dl_conv_forward: phase_kbase must be a multiple of 64");

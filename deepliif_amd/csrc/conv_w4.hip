@@ -58,8 +58,15 @@ static_assert(W4_LDS <= 160 * 1024, "the whole LDS of a CU");
 //            + one piece per shadow;  bit 1: the barrier of a step sits in the MIDDLE of sub-step 3 (after 8 of its MFMAs) instead of in front of it.
 // ABL != 0: timing-only ablations (results wrong by construction): 1 = no DMA in the loop, 2 = DMA only, 3 = MFMAs only, 4 = no K loop (prologue
 //           + epilogue), 5 = DMA issued but never waited for
-template <bool FLIP, int VAR, int ABL>
+// BORDER: DL_PAD_ZERO -- the off-image rows come from the zero resource and the off-row fragment lane is zeroed in registers (above).  A border that COPIES
+//           a pixel (border_idx, common.h: DL_PAD_REPLICATE clamps; a mirror would be one more instantiation) changes only WHICH image row a slab row is staged from
+//           -- always one of the tile's own image, so the zero resource is never used -- and WHICH LDS address the one off-row lane reads for that one
+//           fragment: a second, loop-invariant fragment base (axe) with the swizzle of the redirected slab row.  No extra DMA piece, no select in the loop.
+//           Forward tap order only (w4_eligible): the data gradient of such a layer is the pad-0 plan over the padded extent + a fold.
+template <bool FLIP, int VAR, int ABL, int BORDER = DL_PAD_ZERO>
 __global__ void __launch_bounds__(256) conv_gemm_w4_kernel(const ConvArgs a) {
+    constexpr bool COPY = BORDER != DL_PAD_ZERO;
+    static_assert(!(COPY && FLIP), "a copying border is built for the forward tap order only");
     constexpr bool SEP = (VAR & 1) != 0, LATE = (VAR & 2) != 0;
     constexpr bool DMA_ON = ABL != 1 && ABL != 3;
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
@@ -104,8 +111,13 @@ __global__ void __launch_bounds__(256) conv_gemm_w4_kernel(const ConvArgs a) {
 
     // uniform part of the activation source address of group (chunk c, kernel row kh), and whether that image row exists for this wave
     auto x_group_base = [&](int c, int kh, bool &valid) __attribute__((always_inline)) {
-        const int dh = kh == 0 ? dhs[0] : (kh == 1 ? dhs[1] : dhs[2]);
-        valid = (unsigned)(h0 + R + dh) < (unsigned)a.Hi;
+        int dh = kh == 0 ? dhs[0] : (kh == 1 ? dhs[1] : dhs[2]);
+        if constexpr (COPY) {              // the row this wave stages is a row of the tile's OWN image: h0 + R < Hi, and the map stays inside [0, Hi)
+            dh = border_idx(BORDER, h0 + R + dh, a.Hi) - (h0 + R);
+            valid = true;
+        } else {
+            valid = (unsigned)(h0 + R + dh) < (unsigned)a.Hi;
+        }
         return xg + ((ptrdiff_t)dh * a.Wi * a.in_pstride + c * 64) * 2;
     };
     // VAR bit 2 / bit 3: weight / activation pieces by buffer_load ... lds (resource in SGPRs, loop-invariant 32-bit lane offset, the per-step
@@ -149,6 +161,14 @@ __global__ void __launch_bounds__(256) conv_gemm_w4_kernel(const ConvArgs a) {
         axk[k] = W4_X0 + row * 128 + ((lh ^ ((row >> 1) & 7)) << 4);
     }
     const bool edge_lo = lr == 0, edge_hi = lr == 31;                   // the lane whose pixel is column -1 (block 0, dw = -1) / 128 (block 3, dw = +1)
+    // COPY: fragment base of the ONE fragment per outer tap that holds the off-row pixel -- block 0 at shift -1 (axe[0]), block 3 at shift +1 (axe[1], the
+    // block's 3 * 4096 bytes taken off again) -- equal to axk[] in every lane but the edge lane, which reads the border map's pixel of the SAME slab row
+    int axe[2] = {0, 0};
+    if constexpr (COPY) {
+        const int row_lo = wm * 128 + border_idx(BORDER, -1, 128), row_hi = wm * 128 + border_idx(BORDER, 128, 128);
+        axe[0] = edge_lo ? W4_X0 + row_lo * 128 + ((lh ^ ((row_lo >> 1) & 7)) << 4) : axk[0];
+        axe[1] = edge_hi ? W4_X0 + row_hi * 128 + ((lh ^ ((row_hi >> 1) & 7)) << 4) - 3 * 4096 : axk[2];
+    }
 
     f32x16_t acc[4][4];
 #pragma unroll
@@ -166,10 +186,12 @@ __global__ void __launch_bounds__(256) conv_gemm_w4_kernel(const ConvArgs a) {
             FB[f] = bf16x8_t{(short)(0x3f00 + lane), (short)(0x3f80 + f), 0x3e90, 0x3f01, (short)0xbf00, 0x3f20, 0x3e80, 0x3f11};
         }
     }
-    auto read_one = [&](auto FI, int wp, int xp, bf16x8_t (&F)[8]) __attribute__((always_inline)) {
-        constexpr int f = decltype(FI)::value;
+    // xe: base of the edge fragment of the step the fragments belong to (COPY only; EF = that fragment's index, 0 = none: the centre tap)
+    auto read_one = [&](auto FI, int wp, int xp, bf16x8_t (&F)[8], auto EFc, int xe) __attribute__((always_inline)) {
+        constexpr int f = decltype(FI)::value, EF = decltype(EFc)::value;
         if constexpr (ABL == 2 || ABL == 3) return;
         if constexpr (f < 4) F[f] = *reinterpret_cast<lds_frag_t *>(lds + wp + f * 4096);
+        else if constexpr (COPY && EF == f) F[f] = *reinterpret_cast<lds_frag_t *>(lds + xe + (f - 4) * 4096);
         else F[f] = *reinterpret_cast<lds_frag_t *>(lds + xp + (f - 4) * 4096);
     };
     auto mma_one = [&](auto MI, const bf16x8_t (&F)[8]) __attribute__((always_inline)) {
@@ -183,19 +205,19 @@ __global__ void __launch_bounds__(256) conv_gemm_w4_kernel(const ConvArgs a) {
     // the fragment lane that fell off the image row reads a neighbouring buffer: zero it (SH = slab shift of the step the fragments belong to)
     auto fix_edge = [&](auto SHc, bf16x8_t (&F)[8]) __attribute__((always_inline)) {
         constexpr int SH = decltype(SHc)::value;
-        if constexpr (ABL == 2 || ABL == 3) return;
+        if constexpr (ABL == 2 || ABL == 3 || COPY) return;         // COPY: the edge lane has read the border pixel itself
         if constexpr (SH == 0) { if (edge_lo) F[4] = bf16x8_t{0, 0, 0, 0, 0, 0, 0, 0}; }
         if constexpr (SH == 2) { if (edge_hi) F[7] = bf16x8_t{0, 0, 0, 0, 0, 0, 0, 0}; }
     };
     // MFMAs [M0, M1) of a K=16 sub-step on Fc; the fragment reads of the NEXT sub-step (into Fn, bases wp / xp) ride in their shadows when READS;
     // hook(m) is called after MFMA m (DMA issue slots).  Source order = intended issue order; pinned by the sched_group_barriers that follow.
-    auto mfma_range = [&](auto M0c, auto M1c, auto READSc, const bf16x8_t (&Fc)[8], bf16x8_t (&Fn)[8], int wp, int xp, auto &&hook) __attribute__((always_inline)) {
+    auto mfma_range = [&](auto M0c, auto M1c, auto READSc, const bf16x8_t (&Fc)[8], bf16x8_t (&Fn)[8], int wp, int xp, auto &&hook, auto EFc, int xe) __attribute__((always_inline)) {
         constexpr int M0 = decltype(M0c)::value, M1 = decltype(M1c)::value;
         constexpr bool READS = decltype(READSc)::value != 0;
         constexpr int RBASE = decltype(READSc)::value == 2 ? 8 : 0;      // READS == 2: the reads start at MFMA 8 (second half of a sub-step)
         auto rd = [&](auto K) __attribute__((always_inline)) {           // K-th read of the sub-step: W0 X0 W1 X1 W2 X2 W3 X3
             constexpr int k = decltype(K)::value;
-            read_one(W4IC<(k & 1) ? 4 + (k >> 1) : (k >> 1)>{}, wp, xp, Fn);
+            read_one(W4IC<(k & 1) ? 4 + (k >> 1) : (k >> 1)>{}, wp, xp, Fn, EFc, xe);
         };
         auto one = [&](auto MI) __attribute__((always_inline)) {
             constexpr int m = decltype(MI)::value;
@@ -269,9 +291,10 @@ __global__ void __launch_bounds__(256) conv_gemm_w4_kernel(const ConvArgs a) {
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");          // slab 0, weights 0 visible (weights 1 still in flight: __syncthreads() would drain them)
 
     if (G > 0) {
-        const int wp = aw + w4_wofs(0), xp = axk[0];
-        read_one(W4IC<0>{}, wp, xp, FA); read_one(W4IC<4>{}, wp, xp, FA); read_one(W4IC<1>{}, wp, xp, FA); read_one(W4IC<5>{}, wp, xp, FA);
-        read_one(W4IC<2>{}, wp, xp, FA); read_one(W4IC<6>{}, wp, xp, FA); read_one(W4IC<3>{}, wp, xp, FA); read_one(W4IC<7>{}, wp, xp, FA);
+        const int wp = aw + w4_wofs(0), xp = axk[0], xe = axe[0];
+        constexpr W4IC<(FLIP ? 7 : 4)> EF0{};                              // step 0's slab shift: -1 in the forward order, block 0 holds the off-row pixel
+        read_one(W4IC<0>{}, wp, xp, FA, EF0, xe); read_one(W4IC<4>{}, wp, xp, FA, EF0, xe); read_one(W4IC<1>{}, wp, xp, FA, EF0, xe); read_one(W4IC<5>{}, wp, xp, FA, EF0, xe);
+        read_one(W4IC<2>{}, wp, xp, FA, EF0, xe); read_one(W4IC<6>{}, wp, xp, FA, EF0, xe); read_one(W4IC<3>{}, wp, xp, FA, EF0, xe); read_one(W4IC<7>{}, wp, xp, FA, EF0, xe);
     }
 
     // K step t = 3 g + KW of group g: see the header comment
@@ -282,6 +305,10 @@ __global__ void __launch_bounds__(256) conv_gemm_w4_kernel(const ConvArgs a) {
         const int wcur = aw + w4_wofs(KW), xcur = axk[KW] + xs;
         const int wnext = aw + w4_wofs((KW + 1) % 3);
         const int xnext = KW < 2 ? axk[(KW + 1) % 3] + xs : axk[0] + xsn;
+        // COPY: edge fragment of this step / of the next one (slab shift 0 -> fragment 4, 2 -> fragment 7, 1 -> none) and its base
+        constexpr int EFC = SH == 0 ? 4 : (SH == 2 ? 7 : 0), EFN = SHN == 0 ? 4 : (SHN == 2 ? 7 : 0);
+        const int xecur = COPY ? axe[SH == 2 ? 1 : 0] + xs : 0;
+        const int xenext = COPY ? axe[SHN == 2 ? 1 : 0] + (KW < 2 ? xs : xsn) : 0;
         // W(t+2): KW 0 -> (g, kw 2), KW 1 -> (g+1, kw 0), KW 2 -> (g+1, kw 1); it goes to the buffer step t-1 has just released
         const char *wsrc = KW == 0 ? wgrp + 2 * tap_bytes : (KW == 1 ? wgrp_n : wgrp_n + tap_bytes);
         const int xslab = (g + 1) & 1;
@@ -306,22 +333,22 @@ __global__ void __launch_bounds__(256) conv_gemm_w4_kernel(const ConvArgs a) {
         // fetches it (an s_waitcnt lgkmcnt(0) on a fresh read in the middle of the MFMA stream)
         __builtin_amdgcn_sched_barrier(0);
         fix_edge(W4IC<SH>{}, FA);
-        mfma_range(W4IC<0>{}, W4IC<16>{}, W4IC<1>{}, FA, FB, wcur ^ (1 << 5), xcur ^ (1 << 5), hook_s(W4IC<0>{}));
+        mfma_range(W4IC<0>{}, W4IC<16>{}, W4IC<1>{}, FA, FB, wcur ^ (1 << 5), xcur ^ (1 << 5), hook_s(W4IC<0>{}), W4IC<EFC>{}, xecur ^ (1 << 5));
         pin(W4IC<0>{}, W4IC<16>{}, W4IC<1>{}, W4IC<DMA_ON ? ND0 : 0>{});
         __builtin_amdgcn_sched_barrier(0);
         fix_edge(W4IC<SH>{}, FB);
-        mfma_range(W4IC<0>{}, W4IC<16>{}, W4IC<1>{}, FB, FA, wcur ^ (2 << 5), xcur ^ (2 << 5), hook_s(W4IC<1>{}));
+        mfma_range(W4IC<0>{}, W4IC<16>{}, W4IC<1>{}, FB, FA, wcur ^ (2 << 5), xcur ^ (2 << 5), hook_s(W4IC<1>{}), W4IC<EFC>{}, xecur ^ (2 << 5));
         pin(W4IC<0>{}, W4IC<16>{}, W4IC<1>{}, W4IC<DMA_ON ? ND1 : 0>{});
         __builtin_amdgcn_sched_barrier(0);
         fix_edge(W4IC<SH>{}, FA);
-        if constexpr (ND2 > 0) mfma_range(W4IC<0>{}, W4IC<16>{}, W4IC<1>{}, FA, FB, wcur ^ (3 << 5), xcur ^ (3 << 5), hook_s(W4IC<2>{}));
-        else mfma_range(W4IC<0>{}, W4IC<16>{}, W4IC<1>{}, FA, FB, wcur ^ (3 << 5), xcur ^ (3 << 5), nohook);
+        if constexpr (ND2 > 0) mfma_range(W4IC<0>{}, W4IC<16>{}, W4IC<1>{}, FA, FB, wcur ^ (3 << 5), xcur ^ (3 << 5), hook_s(W4IC<2>{}), W4IC<EFC>{}, xecur ^ (3 << 5));
+        else mfma_range(W4IC<0>{}, W4IC<16>{}, W4IC<1>{}, FA, FB, wcur ^ (3 << 5), xcur ^ (3 << 5), nohook, W4IC<EFC>{}, xecur ^ (3 << 5));
         pin(W4IC<0>{}, W4IC<16>{}, W4IC<1>{}, W4IC<DMA_ON ? ND2 : 0>{});
         __builtin_amdgcn_sched_barrier(0);
         fix_edge(W4IC<SH>{}, FB);
         // everything but the 8 youngest pieces (= W(t+2)) has landed: W(t+1), the slab pieces of this step; this wave's reads of buffer t are complete
         if constexpr (LATE) {
-            mfma_range(W4IC<0>{}, W4IC<8>{}, W4IC<0>{}, FB, FA, wnext, xnext, nohook);
+            mfma_range(W4IC<0>{}, W4IC<8>{}, W4IC<0>{}, FB, FA, wnext, xnext, nohook, W4IC<EFN>{}, xenext);
             pin(W4IC<0>{}, W4IC<8>{}, W4IC<0>{}, W4IC<0>{});
             __builtin_amdgcn_sched_barrier(0);          // keeps those 8 MFMAs in front of the barrier (register-only instructions may cross an asm)
         }
@@ -329,10 +356,10 @@ __global__ void __launch_bounds__(256) conv_gemm_w4_kernel(const ConvArgs a) {
         else if constexpr (DMA_ON) asm volatile("s_waitcnt vmcnt(8) lgkmcnt(0)\n\ts_barrier" ::: "memory");
         else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
         if constexpr (LATE) {
-            mfma_range(W4IC<8>{}, W4IC<16>{}, W4IC<2>{}, FB, FA, wnext, xnext, nohook);
+            mfma_range(W4IC<8>{}, W4IC<16>{}, W4IC<2>{}, FB, FA, wnext, xnext, nohook, W4IC<EFN>{}, xenext);
             pin(W4IC<8>{}, W4IC<16>{}, W4IC<2>{}, W4IC<0>{});
         } else {
-            mfma_range(W4IC<0>{}, W4IC<16>{}, W4IC<1>{}, FB, FA, wnext, xnext, nohook);
+            mfma_range(W4IC<0>{}, W4IC<16>{}, W4IC<1>{}, FB, FA, wnext, xnext, nohook, W4IC<EFN>{}, xenext);
             pin(W4IC<0>{}, W4IC<16>{}, W4IC<1>{}, W4IC<0>{});
         }
         (void)SHN;
@@ -506,13 +533,13 @@ __global__ void __launch_bounds__(256) conv_gemm_w4_kernel(const ConvArgs a) {
 static bool w4_flipped(const ConvArgs &a) { return (int8_t)((a.taps[0] >> 8) & 0xff) == 1; }
 
 // The layers this kernel serves: one phase of 9 taps ordered (kh, kw) with dh constant per kernel row and the SAME dw order (-1, 0, +1 or reversed:
-// the data gradient) in every row, stride 1, image rows exactly 128 pixels wide (a 256-pixel tile = two whole image rows), zero padding,
+// the data gradient) in every row, stride 1, image rows exactly 128 pixels wide (a 256-pixel tile = two whole image rows), zero padding (or replicate padding in the forward tap order),
 // Cin a multiple of 64, Co a multiple of 256, epilogue activation none / ReLU, bf16 result (no split-K / raw accumulators / fused norm-backward reductions).
 bool w4_eligible(const ConvArgs &a) {
     if (a.n_phase != 1 || a.splitk != 1 || a.raw_out || a.in_step != 1 || a.out_step != 1 || a.Wq != 128 || a.Wi != 128 || (a.Hq & 1)) return false;
     if (a.Ho != a.Hq || a.Wo != a.Wq || a.Hi != a.Hq) return false;
     if (a.phase_tap_begin[1] - a.phase_tap_begin[0] != 9 || a.phase_tap_begin[0] != 0) return false;
-    if (a.Ci < 64 || (a.Ci & 63) || (a.Co & 255) || a.pad_mode != DL_PAD_ZERO || a.in_act != DL_ACT_NONE) return false;
+    if (a.Ci < 64 || (a.Ci & 63) || (a.Co & 255) || (a.pad_mode != DL_PAD_ZERO && a.pad_mode != DL_PAD_REPLICATE) || a.in_act != DL_ACT_NONE) return false;
     if (a.act != DL_ACT_NONE && a.act != DL_ACT_RELU) return false;
     if ((size_t)a.Hi * a.Wi * (size_t)a.in_pstride * 2 >= ((size_t)1 << 31) || (size_t)256 * a.w_kstride * 2 >= ((size_t)1 << 31)) return false;   // 32-bit lane offsets
     int seen = 0;
@@ -528,12 +555,13 @@ bool w4_eligible(const ConvArgs &a) {
     }
     const int d0 = (int8_t)((a.taps[0] >> 8) & 0xff), d1 = (int8_t)((a.taps[1] >> 8) & 0xff), d2 = (int8_t)((a.taps[2] >> 8) & 0xff);
     if (!((d0 == -1 && d1 == 0 && d2 == 1) || (d0 == 1 && d1 == 0 && d2 == -1))) return false;
+    if (a.pad_mode != DL_PAD_ZERO && d0 != -1) return false;             // a copying border: forward tap order only (conv_gemm_w4_kernel<.., BORDER>)
     return seen == 7;
 }
 
-template <bool FLIP, int VAR, int ABL>
+template <bool FLIP, int VAR, int ABL, int BORDER = DL_PAD_ZERO>
 static int launch_w4(const ConvArgs &a, hipStream_t stream) {
-    auto kern = conv_gemm_w4_kernel<FLIP, VAR, ABL>;
+    auto kern = conv_gemm_w4_kernel<FLIP, VAR, ABL, BORDER>;
     static bool attr_set = false;
     if (!attr_set) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)W4_LDS);
@@ -546,14 +574,18 @@ static int launch_w4(const ConvArgs &a, hipStream_t stream) {
     return 0;
 }
 
-template <int VAR, int ABL>
-static int launch_w4_dir(const ConvArgs &a, hipStream_t stream) {
-    return w4_flipped(a) ? launch_w4<true, VAR, ABL>(a, stream) : launch_w4<false, VAR, ABL>(a, stream);
-}
-
 #ifndef DL_W4_DEFAULT_VAR
 #define DL_W4_DEFAULT_VAR 13
 #endif
+
+template <int VAR, int ABL>
+static int launch_w4_dir(const ConvArgs &a, hipStream_t stream) {
+    if (a.pad_mode == DL_PAD_REPLICATE) {
+        if constexpr (ABL == 0 && VAR == DL_W4_DEFAULT_VAR) return launch_w4<false, VAR, 0, DL_PAD_REPLICATE>(a, stream);
+        else DL_FAIL("dl_conv_forward(w4): the schedule variants and ablations exist for zero padding only");
+    }
+    return w4_flipped(a) ? launch_w4<true, VAR, ABL>(a, stream) : launch_w4<false, VAR, ABL>(a, stream);
+}
 
 int launch_conv_w4(const ConvArgs &a0, hipStream_t stream) {
     ConvArgs a = a0;

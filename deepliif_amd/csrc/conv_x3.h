@@ -666,7 +666,7 @@ __global__ void __launch_bounds__(WM * WN * 64) conv_gemm_glds_x3_kernel(const C
                     const int16_t t = tap_lds[tap0 + tli];
                     const int dh = (int)(int8_t)(t & 0xff), dw = (int)(int8_t)((t >> 8) & 0xff);
                     int hi = x_hi0[i] + dh, wi = x_wi0[i] + dw;
-                    if (a.pad_mode == DL_PAD_REFLECT) { hi = reflect_idx(hi, a.Hi); wi = reflect_idx(wi, a.Wi); }
+                    if (a.pad_mode != DL_PAD_ZERO) { hi = border_idx(a.pad_mode, hi, a.Hi); wi = border_idx(a.pad_mode, wi, a.Wi); }
                     const bool ok = x_ok[i] && (tl < ntaps) && ((unsigned)hi < (unsigned)a.Hi) && ((unsigned)wi < (unsigned)a.Wi);
                     const ptrdiff_t off = ((ptrdiff_t)(hi - x_hi0[i]) * a.Wi + (wi - x_wi0[i])) * (ptrdiff_t)a.in_pstride + ci - x_chunk[i] * 4;
                     const float *src = ok ? x_ptr[i] + off : zero;
@@ -904,7 +904,7 @@ __global__ void __launch_bounds__(256, 2) conv_c4_patch_x3_kernel(const C4Args c
             const int i = tid + k * 256;
             const int pr = i / (TC + KR), pc = i - pr * (TC + KR);
             int hi = th * TR - 3 + pr, wi = tw * TC - 3 + pc;
-            if (PADMODE == DL_PAD_REFLECT) { hi = reflect_idx(hi, a.Hi); wi = reflect_idx(wi, a.Wi); }
+            if (PADMODE != DL_PAD_ZERO) { hi = border_idx(PADMODE, hi, a.Hi); wi = border_idx(PADMODE, wi, a.Wi); }
             const bool ok = i < PR * (TC + KR) && (unsigned)hi < (unsigned)a.Hi && (unsigned)wi < (unsigned)a.Wi;
             f32x4_t v = {0.f, 0.f, 0.f, 0.f};
             if (ok) v = *reinterpret_cast<const f32x4_t *>(in + ((size_t)(n * a.Hi + hi) * a.Wi + wi) * 8);
@@ -1036,11 +1036,13 @@ static int launch_conv_c4_x3(const ConvArgs &a0, const dl_conv_desc *d, hipStrea
     c4_fill_args(ca, a0, d);
     constexpr size_t smem = 4 * ((4 + 6) * 72 * 8 + 16) + 4 * 64 * sizeof(float);      // four patch copies + statistics
     void (*kern)(const C4Args) = nullptr;
-    const bool refl = d->pad_mode == DL_PAD_REFLECT;
+    // one instantiation per (border, activation): d->pad_mode was validated by dl_conv_forward (0 .. 2)
+#define DL_C4_PICK(ACT) (d->pad_mode == DL_PAD_REFLECT ? conv_c4_patch_x3_kernel<DL_PAD_REFLECT, ACT> : (d->pad_mode == DL_PAD_REPLICATE ? conv_c4_patch_x3_kernel<DL_PAD_REPLICATE, ACT> : conv_c4_patch_x3_kernel<DL_PAD_ZERO, ACT>))
     switch (d->act) {
-        case DL_ACT_RELU: kern = refl ? conv_c4_patch_x3_kernel<DL_PAD_REFLECT, DL_ACT_RELU> : conv_c4_patch_x3_kernel<DL_PAD_ZERO, DL_ACT_RELU>; break;
-        case DL_ACT_LRELU: kern = refl ? conv_c4_patch_x3_kernel<DL_PAD_REFLECT, DL_ACT_LRELU> : conv_c4_patch_x3_kernel<DL_PAD_ZERO, DL_ACT_LRELU>; break;
-        default: kern = refl ? conv_c4_patch_x3_kernel<DL_PAD_REFLECT, DL_ACT_NONE> : conv_c4_patch_x3_kernel<DL_PAD_ZERO, DL_ACT_NONE>; break;
+        case DL_ACT_RELU: kern = DL_C4_PICK(DL_ACT_RELU); break;
+        case DL_ACT_LRELU: kern = DL_C4_PICK(DL_ACT_LRELU); break;
+        default: kern = DL_C4_PICK(DL_ACT_NONE); break;
     }
+#undef DL_C4_PICK
     return c4_launch(kern, ca, d, smem, stream, "dl_conv_forward(c4 patch x3)");
 }

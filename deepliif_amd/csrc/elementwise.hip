@@ -641,10 +641,6 @@ extern "C" int dl_dropout(int dtype, const void *x, int x_ps, void *y, int y_ps,
 }
 
 // ------------------------------------------------------------------------------------------- narrow-Cout conv helpers
-__device__ __forceinline__ int reflect_w(int i, int n) {
-    i = i < 0 ? -i : i;
-    return i >= n ? 2 * n - 2 - i : i;
-}
 // y[n,h,w,co] = act(bias[co] + sum_kw T[n,h,w+kw-pad,co*KW+kw]); pad channels of y are zeroed.
 // One block = SS_PIX consecutive pixels of one image row: the T rows (Tc fp32 channels per pixel) of those pixels plus the
 // (KW-1) halo are staged through LDS with coalesced 16-byte loads, then each thread sums its pixel's Cout*KW taps.
@@ -666,7 +662,7 @@ __global__ void __launch_bounds__(256) shift_sum_kernel(const float *Tm, int N, 
         int ws = w0 - pad + i;
         float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
         bool ok = (unsigned)ws < (unsigned)W;
-        if (pad_mode == DL_PAD_REFLECT) { ws = reflect_w(ws, W); ok = true; }
+        if (pad_mode != DL_PAD_ZERO) { ws = border_idx(pad_mode, ws, W); ok = true; }
         if (ok) v = *reinterpret_cast<const float4 *>(Tm + (row * W + ws) * Tc + c);
         float *d = tile + i * ld + c;
         d[0] = v.x; d[1] = v.y; d[2] = v.z; d[3] = v.w;
@@ -687,6 +683,7 @@ extern "C" int dl_shift_sum(const float *Tm, int N, int H, int W, int Tc, int Co
                             int out_dtype, void *out, int o_ps, int oCp, void *stream_) {
     hipStream_t stream = (hipStream_t)stream_;
     if (!Tm || !out || Cout * KW > Tc || Tc % 4) DL_FAIL("dl_shift_sum: bad argument");
+    if (pad_mode < DL_PAD_ZERO || pad_mode > DL_PAD_REPLICATE) DL_FAIL("dl_shift_sum: pad_mode=%d (0 zero | 1 reflect | 2 replicate)", pad_mode);
     const int segs = (W + SS_PIX - 1) / SS_PIX;
     const size_t blocks = (size_t)N * H * segs;
     const size_t smem = (size_t)(SS_PIX + KW - 1) * (Tc + 1) * sizeof(float);
@@ -855,5 +852,51 @@ extern "C" int dl_reflect_fold(int dtype, const void *src, int src_pstride, void
     else if (dtype == DL_BF16) hipLaunchKernelGGL(reflect_fold_kernel<bf16_t>, dim3(EW_BLOCKS(total)), dim3(256), 0, stream, (const bf16_t *)src, src_pstride, (bf16_t *)dst, dst_pstride, N, H, W, pad, Cp);
     else DL_FAIL("dl_reflect_fold: dtype %d", dtype);
     DL_CHECK_LAUNCH("dl_reflect_fold");
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------- replication-pad backward (fold)
+// dst[n,h,w,:] = sum of src[n,hp,wp,:] over every position of the replication-padded extent (H+2p) x (W+2p) whose clamp is (h,w): padded rows
+// 0 .. p for h = 0, H-1+p .. H-1+2p for h = H-1 (0 .. 2p when H = 1), the one row h+p otherwise; same along w.  Rows outer, columns inner, ascending:
+// a fixed order, fp32.  src = the data gradient with respect to the explicitly padded input (dl_conv_forward with the pad-0 plan).
+template <typename TS, typename T>
+__global__ void __launch_bounds__(256) replicate_fold_kernel(const TS *src, int s_ps, T *dst, int d_ps, int N, int H, int W, int p, int Cp) {
+    const int cvec = Cp / 8;
+    const int Hp = H + 2 * p, Wp = W + 2 * p;
+    const size_t total = (size_t)N * H * W * cvec;
+    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+        const int c0 = (int)(i % cvec) * 8;
+        size_t pix = i / cvec;
+        const int w = (int)(pix % W);
+        pix /= W;
+        const int h = (int)(pix % H), n = (int)(pix / H);
+        const int h_lo = h == 0 ? 0 : h + p, h_hi = h == H - 1 ? Hp - 1 : h + p;
+        const int w_lo = w == 0 ? 0 : w + p, w_hi = w == W - 1 ? Wp - 1 : w + p;
+        float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        for (int a = h_lo; a <= h_hi; ++a)
+            for (int b = w_lo; b <= w_hi; ++b) {
+                float v[8];
+                Vec8<TS>::load(src + (((size_t)n * Hp + a) * Wp + b) * s_ps + c0, v);
+#pragma unroll
+                for (int k = 0; k < 8; ++k) acc[k] += v[k];
+            }
+        Vec8<T>::store(dst + (((size_t)n * H + h) * W + w) * d_ps + c0, acc);
+    }
+}
+extern "C" int dl_replicate_fold(int dtype, const void *src, int src_pstride, void *dst, int dst_pstride, int N, int H, int W, int pad, int Cp,
+                                 void *stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (N <= 0 || H <= 0 || W <= 0) DL_FAIL("dl_replicate_fold: empty problem (N=%d, %dx%d): nothing to launch", N, H, W);
+    if (!src || !dst || Cp <= 0 || Cp % 8 || src_pstride % 8 || dst_pstride % 8) DL_FAIL("dl_replicate_fold: bad argument");
+    if (pad < 1) DL_FAIL("dl_replicate_fold: pad=%d must be >= 1", pad);
+    const size_t total = (size_t)N * H * W * (Cp / 8);
+    if (dtype == DL_F32 || dtype == (DL_F32 | DL_FOLD_SRC_F32))
+        hipLaunchKernelGGL((replicate_fold_kernel<float, float>), dim3(EW_BLOCKS(total)), dim3(256), 0, stream, (const float *)src, src_pstride, (float *)dst, dst_pstride, N, H, W, pad, Cp);
+    else if (dtype == DL_BF16)
+        hipLaunchKernelGGL((replicate_fold_kernel<bf16_t, bf16_t>), dim3(EW_BLOCKS(total)), dim3(256), 0, stream, (const bf16_t *)src, src_pstride, (bf16_t *)dst, dst_pstride, N, H, W, pad, Cp);
+    else if (dtype == (DL_BF16 | DL_FOLD_SRC_F32))
+        hipLaunchKernelGGL((replicate_fold_kernel<float, bf16_t>), dim3(EW_BLOCKS(total)), dim3(256), 0, stream, (const float *)src, src_pstride, (bf16_t *)dst, dst_pstride, N, H, W, pad, Cp);
+    else DL_FAIL("dl_replicate_fold: dtype %d", dtype);
+    DL_CHECK_LAUNCH("dl_replicate_fold");
     return 0;
 }

@@ -42,11 +42,6 @@ struct WgradLayers {
     float *slab[WGRAD_MULTI_MAX];
 };
 
-__device__ __forceinline__ int reflect_idx_w(int i, int n) {
-    i = i < 0 ? -i : i;
-    return i >= n ? 2 * n - 2 - i : i;
-}
-
 template <typename T> struct RawW;
 template <> struct RawW<bf16_t> { u32x4_t v; };
 template <> struct RawW<float> { f32x4_t a, b; };
@@ -173,7 +168,7 @@ __global__ void __launch_bounds__(256) wgrad_kernel(const WgradArgs a) {
             const int p = pbase + (tid >> 4) + i * 16;
             int h = qh[i] * a.step - a.pad + kh, w = qw[i] * a.step - a.pad_w + kw;
             bool ok = tap_ok && p < p_end;
-            if (a.pad_mode == DL_PAD_REFLECT) { h = reflect_idx_w(h, a.Hq); w = reflect_idx_w(w, a.Wq); }
+            if (a.pad_mode != DL_PAD_ZERO) { h = border_idx(a.pad_mode, h, a.Hq); w = border_idx(a.pad_mode, w, a.Wq); }
             else ok = ok && ((unsigned)h < (unsigned)a.Hq) && ((unsigned)w < (unsigned)a.Wq);
             if (ok) raww_load<T>(qr[i], Q + ((size_t)(qn[i] * a.Hq + h) * a.Wq + w) * a.q_pstride + cb);
             else raww_zero<T>(qr[i]);
@@ -938,6 +933,8 @@ static int wgrad_slabs(const dl_wgrad_desc *d, const WgradLayers &lay, int n, hi
     if (d->splitk < 1) DL_FAIL("dl_conv_wgrad: splitk=%d", d->splitk);
     if (d->stack_kw && d->KW != 1) DL_FAIL("dl_conv_wgrad: stack_kw needs KW == 1");
     if (d->prec == DL_PREC_BF16X3 && d->dtype != DL_F32) DL_FAIL("dl_conv_wgrad: BF16X3 needs fp32 activations");
+    if (d->pad_mode < DL_PAD_ZERO || d->pad_mode > DL_PAD_REPLICATE) DL_FAIL("dl_conv_wgrad: pad_mode=%d (0 zero | 1 reflect | 2 replicate)", d->pad_mode);
+    if (d->pad_mode == DL_PAD_REPLICATE && d->step != 1) DL_FAIL("dl_conv_wgrad: replicate padding only for step == 1 layers (step=%d)", d->step);
 
     WgradArgs a;
     memset(&a, 0, sizeof(a));

@@ -39,7 +39,17 @@ constexpr int W4W_X0 = 2 * W4W_DY;
 constexpr size_t W4W_LDS = (size_t)2 * W4W_DY + 2 * W4W_X;
 static_assert(W4W_LDS <= 160 * 1024, "LDS of a CU");
 
+// BORDER: DL_PAD_ZERO as described above.  A border that COPIES a pixel (DL_PAD_REPLICATE; a mirror would be one more instantiation): no image row is
+// skipped -- the x row staged for row h is border_idx(h + dh) of the row's OWN image (r % H decides: row ranges may start and end mid-image) -- and LDS pixel
+// rows 0 and 129 of the x buffer hold the border map's pixel of the row just staged instead of zeros.  They arrive by ONE more DMA piece per wave and row
+// (waves 0, 1: LDS rows 0..3 = pixels b(-1), 0, 1, 2; waves 2, 3: LDS rows 126..129 = pixels 125, 126, 127, b(128); the three interior rows of the piece
+// repeat what the regular pieces write, bit for bit), issued in the row's last free DMA shadow: the step ends with vmcnt(0), so no count changes, and the
+// transposing reads (and with them the inline-asm contract tests/test_isa_checks.py holds) are the zero instantiation's.  The alternative -- redirecting the
+// lane addresses of the transposing reads of sub-steps 0 and 7 -- needs two more address registers per lane and a second form of those two sub-steps inside the
+// pinned read stream; it was not built.
+template <int BORDER>
 __global__ void __launch_bounds__(256) wgrad_w4_kernel(const WgradW4Args a, const WgradLayers lay) {
+    constexpr bool COPY = BORDER != DL_PAD_ZERO;
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     w4w_lds_t *lds = (w4w_lds_t *)smem_raw;
 
@@ -76,9 +86,16 @@ __global__ void __launch_bounds__(256) wgrad_w4_kernel(const WgradW4Args a, cons
     const __amdgpu_buffer_rsrc_t rsrc_p = __builtin_amdgcn_make_buffer_rsrc(const_cast<char *>(Pg), 0, 0x7fffffff, 0x00020000);
     const __amdgpu_buffer_rsrc_t rsrc_q = __builtin_amdgcn_make_buffer_rsrc(const_cast<char *>(Qg), 0, 0x7fffffff, 0x00020000);
     int sp = 0, sq = 0;                                                              // scalar offsets of the row being staged (+ this wave's share)
+    int sqe = 0;                                                                     // COPY: scalar offset of the staged x row itself (edge piece)
     auto set_row = [&](int r) __attribute__((always_inline)) {
         sp = r * p_row + wave * 8 * p_piece;
-        sq = (r + dh) * q_row + wave * 8 * q_piece;
+        if constexpr (COPY) {
+            const int h = r % a.H;
+            sqe = (r - h + border_idx(BORDER, h + dh, a.H)) * q_row;
+            sq = sqe + wave * 8 * q_piece;
+        } else {
+            sq = (r + dh) * q_row + wave * 8 * q_piece;
+        }
     };
     // LDS byte offsets of the buffers: `nb_*` = the buffer being staged (scalar, toggles every row); the fragment addresses below point into the
     // buffer being multiplied and are moved by +-W4W_DY / +-W4W_X at every row (no second copy of the loop body for the other buffer parity: with the
@@ -92,6 +109,12 @@ __global__ void __launch_bounds__(256) wgrad_w4_kernel(const WgradW4Args a, cons
         constexpr int j = decltype(Jc)::value;
         __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_q, (__attribute__((address_space(3))) void *)(lds + W4W_X0 + nb_x + 256 + (wave * 8 + j) * 1024), 16, vq, sq + j * q_piece,
                                                  0, 0);
+    };
+    // COPY: the edge piece of this wave (see the kernel's header): lane l -> LDS row e0 + (l >> 4) of the x buffer, whose pixel is border_idx(row - 1)
+    const int e0 = wave < 2 ? 0 : 126;
+    const int ve = COPY ? border_idx(BORDER, e0 + lq - 1, 128) * a.q_pstride * 2 + ((lc ^ (((e0 + lq) & 3) << 2)) << 4) : 0;
+    auto dma_edge = [&]() __attribute__((always_inline)) {
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_q, (__attribute__((address_space(3))) void *)(lds + W4W_X0 + nb_x + e0 * 256), 16, ve, sqe, 0, 0);
     };
     // piece k (0..15) of a row: dy pieces and x pieces alternate
     auto piece = [&](auto Kc) __attribute__((always_inline)) {
@@ -159,6 +182,7 @@ __global__ void __launch_bounds__(256) wgrad_w4_kernel(const WgradW4Args a, cons
             mma_one(Qc, Fc);
             if constexpr (q < 7) read_frag(Qc, OFS, Fn);
             if constexpr (D0 >= 0 && q >= 7 && q < 11) piece(W4WIC<(D0 >= 0 && q >= 7 && q < 11) ? D0 + q - 7 : 0>{});
+            if constexpr (COPY && D0 == 12 && q == 11) dma_edge();            // behind the row's last regular piece
             __builtin_amdgcn_sched_barrier(0);
         };
         one(W4WIC<0>{}); one(W4WIC<1>{}); one(W4WIC<2>{}); one(W4WIC<3>{}); one(W4WIC<4>{}); one(W4WIC<5>{});
@@ -185,20 +209,21 @@ __global__ void __launch_bounds__(256) wgrad_w4_kernel(const WgradW4Args a, cons
         substep(FB, FA, W4WIC<0>{}, W4WIC<-1>{});
     };
 
-    // ---- prologue: padding columns of both x buffers, first row into buffer 0
-    {
+    // ---- prologue: padding columns of both x buffers (COPY: staged with every row), first row into buffer 0
+    if constexpr (!COPY) {
         const int which = tid >> 6;                                   // (buffer, pixel row -1 | 128)
         *reinterpret_cast<__attribute__((address_space(3))) uint32_t *>(lds + W4W_X0 + (which >> 1) * W4W_X + (which & 1) * 129 * 256 + (tid & 63) * 4) = 0u;
     }
-    // valid rows of this range: every row but, for kh = 0 / 2, the first / last row of an image
+    // valid rows of this range: every row but, for kh = 0 / 2, the first / last row of an image (COPY: every row has its x row)
     int nrows = max(0, r_end - r_begin);
-    if (dh != 0 && nrows > 0) {
+    if (!COPY && dh != 0 && nrows > 0) {
         const int hbad = dh < 0 ? 0 : a.H - 1;                       // rows q with q % H == hbad have no x row
         nrows -= (r_end + a.H - 1 - hbad) / a.H - (r_begin + a.H - 1 - hbad) / a.H;
     }
-    int r = next_valid(r_begin);
+    int r = COPY ? r_begin : next_valid(r_begin);
     if (nrows > 0) {
         set_row(r);
+        if constexpr (COPY) dma_edge();
         piece(W4WIC<0>{}); piece(W4WIC<1>{}); piece(W4WIC<2>{}); piece(W4WIC<3>{}); piece(W4WIC<4>{}); piece(W4WIC<5>{}); piece(W4WIC<6>{}); piece(W4WIC<7>{});
         piece(W4WIC<8>{}); piece(W4WIC<9>{}); piece(W4WIC<10>{}); piece(W4WIC<11>{}); piece(W4WIC<12>{}); piece(W4WIC<13>{}); piece(W4WIC<14>{}); piece(W4WIC<15>{});
     }
@@ -209,7 +234,7 @@ __global__ void __launch_bounds__(256) wgrad_w4_kernel(const WgradW4Args a, cons
         read_frag(W4WIC<4>{}, W4WIC<0>{}, FA); read_frag(W4WIC<5>{}, W4WIC<0>{}, FA); read_frag(W4WIC<6>{}, W4WIC<0>{}, FA);
         // past the end the last row is staged once more into the idle buffer (no branch around the DMA)
         for (int t = 0; t < nrows; ++t) {
-            const int rn = next_valid(r + 1);
+            const int rn = COPY ? (r + 1 < r_end ? r + 1 : -1) : next_valid(r + 1);
             r = rn < 0 ? r : rn;
             set_row(r);
             step();
@@ -235,7 +260,8 @@ __global__ void __launch_bounds__(256) wgrad_w4_kernel(const WgradW4Args a, cons
 static bool w4w_eligible(const dl_wgrad_desc *d) {
     static const bool off = DL_DEV_ENV("DL_NO_WGRAD_W4") != nullptr;
     if (off) return false;
-    if (d->dtype != DL_BF16 || d->prec != DL_PREC_BF16 || d->p_act != DL_ACT_NONE || d->q_act != DL_ACT_NONE || d->pad_mode != DL_PAD_ZERO) return false;
+    if (d->dtype != DL_BF16 || d->prec != DL_PREC_BF16 || d->p_act != DL_ACT_NONE || d->q_act != DL_ACT_NONE) return false;
+    if (d->pad_mode != DL_PAD_ZERO && d->pad_mode != DL_PAD_REPLICATE) return false;
     if (d->KH != 3 || d->KW != 3 || d->step != 1 || d->pad != 1 || (d->pad_w >= 0 && d->pad_w != 1) || d->stack_kw || d->p_split || d->q_split) return false;
     if (d->Wp != 128 || d->Wq != 128 || d->Hp != d->Hq || d->Hp < 2 || d->N < 1) return false;
     if ((d->CAp % 128) || (d->CBp % 128) || (d->p_pstride % 8) || (d->q_pstride % 8)) return false;
@@ -252,14 +278,16 @@ static int launch_wgrad_w4(const dl_wgrad_desc *d, const WgradLayers &lay, int n
     a.p_pstride = d->p_pstride; a.q_pstride = d->q_pstride;
     a.splitk = d->splitk; a.rps = (a.NH + d->splitk - 1) / d->splitk;
     a.tiles_a = d->CAp / 128; a.tiles_b = d->CBp / 128;
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(wgrad_w4_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)W4W_LDS);
+    const bool copy = d->pad_mode == DL_PAD_REPLICATE;
+    auto kern = copy ? wgrad_w4_kernel<DL_PAD_REPLICATE> : wgrad_w4_kernel<DL_PAD_ZERO>;
+    static bool attr_set[2] = {false, false};
+    if (!attr_set[copy]) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)W4W_LDS);
         if (e != hipSuccess) DL_FAIL("dl_conv_wgrad(w4): hipFuncSetAttribute(%zu): %s", W4W_LDS, hipGetErrorString(e));
-        attr_set = true;
+        attr_set[copy] = true;
     }
     const int grid = a.tiles_a * a.tiles_b * 3 * a.splitk * n;
-    hipLaunchKernelGGL(wgrad_w4_kernel, dim3(grid), dim3(256), W4W_LDS, stream, a, lay);
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), W4W_LDS, stream, a, lay);
     DL_CHECK_LAUNCH("dl_conv_wgrad(w4)");
     return 0;
 }

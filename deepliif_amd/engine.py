@@ -665,7 +665,7 @@ def conv(ctx: Ctx, x: Act, layer: ConvLayer, act: int = L.ACT_NONE, in_act: int 
             if layer.bias is not None and layer.bias.requires_grad and not bias_done:
                 return False
         if x_needs:
-            if spec.kind == 'conv' and spec.pad_mode == L.PAD_REFLECT:
+            if spec.kind == 'conv' and spec.pad_mode != L.PAD_ZERO:
                 return False
             if not be.conv_takes_split(g_like, ctx.prec.prec, L.ACT_NONE, L.PAD_ZERO):
                 return False
@@ -719,13 +719,17 @@ def conv(ctx: Ctx, x: Act, layer: ConvLayer, act: int = L.ACT_NONE, in_act: int 
                               L.PAD_ZERO, xw_act, L.ACT_NONE, ctx.prec.prec, True, **({'p_split': xs is not None, 'q_split': gs is not None} if sp else {}))
             if layer.bias is not None and layer.bias.requires_grad and not y.bias_done:
                 be.channel_sum(g, spec.cout, layer.bias.grad, True)
-        if x_needs and spec.kind == 'conv' and spec.pad_mode == L.PAD_REFLECT:
-            # gradient w.r.t. the explicitly reflection-padded input, then fold the mirrored borders back (dl_reflect_fold)
+        if x_needs and spec.kind == 'conv' and spec.pad_mode != L.PAD_ZERO:
+            # gradient w.r.t. the explicitly reflection- / replication-padded input, then fold the copied borders back onto the pixels they were copied from
+            # (dl_reflect_fold / dl_replicate_fold)
             hp, wp = hi + 2 * spec.pad, wi + 2 * spec.pad
-            dxp = torch.empty((n, hp, wp, x.t.shape[3]), dtype=g.dtype, device=g.device)
-            be.conv_forward(layer.packed_dgrad, g, dxp, hp, wp, None, L.ACT_NONE, L.ACT_NONE, ctx.prec.prec)
+            # replicate under a 16-bit policy: the padded gradient stays in fp32 (the conv's raw accumulators) until the fold has summed the up to four copies
+            # of an edge pixel -- one rounding at dx instead of one per copy and one more behind the sum
+            raw = spec.pad_mode == L.PAD_REPLICATE and g.dtype != torch.float32
+            dxp = torch.empty((n, hp, wp, x.t.shape[3]), dtype=torch.float32 if raw else g.dtype, device=g.device)
+            be.conv_forward(layer.packed_dgrad, g, dxp, hp, wp, None, L.ACT_NONE, L.ACT_NONE, ctx.prec.prec, raw_out=raw)
             dx = torch.empty((n, hi, wi, x.t.shape[3]), dtype=g.dtype, device=g.device)
-            be.reflect_fold(dxp, dx, spec.pad)
+            (be.reflect_fold if spec.pad_mode == L.PAD_REFLECT else be.replicate_fold)(dxp, dx, spec.pad)
             del dxp
             if in_act != L.ACT_NONE:
                 be.act_backward(in_act, dx, x.t, dx)

@@ -78,7 +78,7 @@ class ConvSpec:
     k: int
     stride: int
     pad: int
-    pad_mode: int = L.PAD_ZERO      # reflect = an explicit nn.ReflectionPad2d(pad) in front of a padding=0 Conv2d
+    pad_mode: int = L.PAD_ZERO      # reflect / replicate = an explicit nn.ReflectionPad2d(pad) / nn.ReplicationPad2d(pad) in front of a padding=0 Conv2d
     out_pad: int = 0
 
     def out_hw(self, h, w):
@@ -120,10 +120,10 @@ class ConvSpec:
         k, p, s = self.k, self.pad, self.stride
         if self.kind == 'conv':
             if self.pad_mode != L.PAD_ZERO:
-                # nn.ReflectionPad2d(p) + Conv2d(padding=0): this plan is the gradient with respect to the EXPLICITLY PADDED input
-                # (extent (H+2p) x (W+2p), pad-0 conv: dxp[a,b] = sum dy[a-kh, b-kw] W); dl_reflect_fold then adds the mirrored
-                # borders back onto the interior (engine.conv).  Same packed image as the zero-padding plan, other tap offsets.
-                assert s == 1, 'reflection-padded convs of the reference networks are all stride 1 (networks.py:386-388, 438-440, 478-498)'
+                # nn.ReflectionPad2d(p) / nn.ReplicationPad2d(p) + Conv2d(padding=0): this plan is the gradient with respect to the EXPLICITLY PADDED
+                # input (extent (H+2p) x (W+2p), pad-0 conv: dxp[a,b] = sum dy[a-kh, b-kw] W); dl_reflect_fold / dl_replicate_fold then adds the copied
+                # borders back onto the pixels they were copied from (engine.conv).  Same packed image as the zero-padding plan, other tap offsets.
+                assert s == 1, 'reflection- / replication-padded convs of the reference networks are all stride 1 (networks.py:386-388, 438-440, 478-498)'
                 taps = [(-kh, -kw, kh, kw) for kh in range(k) for kw in range(k)]
                 return GatherPlan(1, [(0, 0)], [taps], 1, 1, L.PAD_ZERO, False, self.cin, self.cout).finish()
             if s == 1:

@@ -153,13 +153,15 @@ class ResnetBlock(nn.Module):
 
     def __init__(self, dim, padding_type, norm_layer, use_dropout, use_bias, use_spectral_norm=False):
         super().__init__()
-        if padding_type not in ('zero', 'reflect'):
-            raise NotImplementedError('padding [%s] is not supported by the MI355X engine' % padding_type)
+        if padding_type not in ('zero', 'reflect', 'replicate'):
+            raise NotImplementedError('padding [%s] is not implemented' % padding_type)       # (the reference's own message, networks.py:485)
         seq: List[nn.Module] = []
         self.idx = {}
         for half in (0, 1):
             if padding_type == 'reflect':
                 seq.append(nn.ReflectionPad2d(1))
+            elif padding_type == 'replicate':
+                seq.append(nn.ReplicationPad2d(1))
             self.idx[f'conv{half}'] = len(seq)
             seq.append(SpectralNorm(nn.Conv2d(dim, dim, kernel_size=3, padding=1 if padding_type == 'zero' else 0, bias=use_bias), use_spectral_norm))
             self.idx[f'norm{half}'] = len(seq)
@@ -209,7 +211,9 @@ class ResnetGenerator(EngineNet):
 
     def _bind(self):
         ngf, k = self.ngf, self.norm_kind
+        # the reference pads stem and head with ZeroPad2d(3) for anything but 'reflect' (networks.py:386-397, 438-441): 'replicate' reaches the blocks only
         pm = L.PAD_REFLECT if self.padding_type == 'reflect' else L.PAD_ZERO
+        pm_blk = L.PAD_REPLICATE if self.padding_type == 'replicate' else pm
         m = self.model
         b = {}
         b['stem'] = (_conv_binding(ConvSpec('conv', self.input_nc, ngf, 7, 1, 3, pm), m[1]), _norm_binding(k, ngf, m[2]))
@@ -226,7 +230,7 @@ class ResnetGenerator(EngineNet):
             ent = []
             for half in (0, 1):
                 cm, nm = cb[blk.idx[f'conv{half}']], cb[blk.idx[f'norm{half}']]
-                ent.append((_conv_binding(ConvSpec('conv', ngf * 4, ngf * 4, 3, 1, 1, pm), cm), _norm_binding(k, ngf * 4, nm)))
+                ent.append((_conv_binding(ConvSpec('conv', ngf * 4, ngf * 4, 3, 1, 1, pm_blk), cm), _norm_binding(k, ngf * 4, nm)))
             b['blocks'].append((ent, blk))
             idx += 1
         b['up'] = []

@@ -396,6 +396,14 @@ class HipBackend:
                 splitk = 1
             else:
                 d.splitk = splitk
+        if auto_split and splitk > 1 and plan.pad_mode == L.PAD_REPLICATE:
+            # a replicate-padded ResnetBlock conv takes conv_gemm_w4_kernel at any tile count (csrc/conv_gemm.hip w4_takes_replicate), and that kernel has no
+            # split-K form: keep the layer on it instead of splitting the per-chunk gather
+            d.splitk = 1
+            if self.lib.dl_conv_kernel_name(C.byref(d)) == b'conv_gemm_w4_kernel':
+                splitk = 1
+            else:
+                d.splitk = splitk
         self._last_conv_desc = d          # diagnostic (bench.py roofline label): the kernel name is asked from the library only when somebody reads last_conv_kernel
         slab = WS.get('conv_slab', splitk * n * ho * wo * cop, x.device) if splitk > 1 else None
         nch, part = 0, None
@@ -799,6 +807,15 @@ class HipBackend:
         n, h, w, cp = dst.shape
         assert src.shape == (n, h + 2 * pad, w + 2 * pad, cp) and src.dtype == dst.dtype
         self.check(self.lib.dl_reflect_fold(dl_dtype(src), _ptr(src), pstride(src), _ptr(dst), pstride(dst), n, h, w, pad, cp, _stream()), 'dl_reflect_fold')
+
+    def replicate_fold(self, src, dst, pad):
+        """dst [N,H,W,Cp] <- gradient of nn.ReplicationPad2d(pad) applied to src [N,H+2p,W+2p,Cp] (every border copy added back onto its edge pixel)"""
+        _need_cuda(src, dst)
+        n, h, w, cp = dst.shape
+        assert src.shape == (n, h + 2 * pad, w + 2 * pad, cp) and (src.dtype == dst.dtype or src.dtype == torch.float32)
+        # an fp32 source under a 16-bit destination: the raw accumulators of conv_forward(raw_out=True) -- the gradient is rounded once, at dst
+        flag = L.FOLD_SRC_F32 if src.dtype != dst.dtype else 0
+        self.check(self.lib.dl_replicate_fold(dl_dtype(dst) | flag, _ptr(src), pstride(src), _ptr(dst), pstride(dst), n, h, w, pad, cp, _stream()), 'dl_replicate_fold')
 
     # ---- tiles: uint8 [H, W, 3] images <-> engine tile batches (crop + transform, is_empty statistic, tensor2im + stitch)
     def tile_gather(self, images, H0, W0, origins, tile, pad, pad_rgb, lut, out):

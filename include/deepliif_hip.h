@@ -35,14 +35,15 @@
 extern "C" {
 #endif
 
-#define DL_VERSION 116
+#define DL_VERSION 117
 
 enum { DL_F32 = 0, DL_BF16 = 1 };           /* DL_BF16 = "the 16-bit type of this library": bfloat16, or IEEE half in libdeepliif_hip_f16.so (below) */
 enum { DL_HALF_BF16 = 0, DL_HALF_FP16 = 1 };   /* dl_half_format() */
 enum { DL_PREC_BF16 = 1, DL_PREC_BF16X3 = 3 };
 enum { DL_ACT_NONE = 0, DL_ACT_RELU = 1, DL_ACT_LRELU = 2, DL_ACT_TANH = 3,       /* LRELU slope 0.2 (networks.py:578,639) */
        DL_ACT_SIGMOID = 4 };   /* nn.Sigmoid of the attention gate (att_unet.py:100-104): elementwise entry points only (dl_act_forward / _backward) */
-enum { DL_PAD_ZERO = 0, DL_PAD_REFLECT = 1 };
+enum { DL_PAD_ZERO = 0, DL_PAD_REFLECT = 1,
+       DL_PAD_REPLICATE = 2 };   /* nn.ReplicationPad2d in front of a padding=0 Conv2d (ResnetBlock, networks.py:482-483 / 499-500): the border copies the edge pixel */
 enum { DL_NORM_INSTANCE = 0, DL_NORM_BATCH = 1 };
 enum { DL_LOSS_BCE_LOGITS = 0, DL_LOSS_MSE = 1, DL_LOSS_SMOOTH_L1 = 2, DL_LOSS_L1 = 3,
        DL_LOSS_LINEAR = 4 };     /* target_const * x: GANLoss('wgangp') = -mean(pred) for real, +mean(pred) for fake (networks.py:307-311) */
@@ -100,7 +101,8 @@ typedef struct dl_conv_desc {
     int32_t phase_tap_begin[DL_MAX_PHASES + 1];
     int32_t phase_kbase[DL_MAX_PHASES];     /* column offset of the phase in a packed weight row (multiple of 64) */
     int8_t tap_dh[DL_MAX_TAPS], tap_dw[DL_MAX_TAPS];
-    int32_t pad_mode;               /* DL_PAD_*: reflect only for single-phase, in_step==1 layers  */
+    int32_t pad_mode;               /* DL_PAD_*: reflect and replicate only for single-phase, in_step==1 layers; any other value is an error.
+                                       Replicate in the forward tap order takes conv_gemm_w4_kernel on the ResnetBlock shape (border inside the kernel) */
     int32_t w_kstride;              /* packed weight row length (elements)                         */
     int32_t w_rows;                 /* packed weight rows (Co rounded up to 128)                   */
     int32_t act;                    /* epilogue activation DL_ACT_*                                */
@@ -160,12 +162,13 @@ const char *dl_conv_kernel_name(const dl_conv_desc *d);
  *   ConvTranspose2d  : P = layer input (a = in channel), Q = dL/dy (b = out channel)   -> IOHW
  * (pixel contraction runs on MFMA via ds_read_b64_tr_b16 transposing LDS reads; split-K slabs combined in a fixed order)
  * Replaces ATen conv backward-weight reached from DeepLIIF_model.py:332,429.
- * slab: fp32 scratch, dl_wgrad_slab_floats(d) elements (splitk slabs of CAp * (KH*KW*CBp), padded apart).  reflect padding of Q is supported (pad_mode).
+ * slab: fp32 scratch, dl_wgrad_slab_floats(d) elements (splitk slabs of CAp * (KH*KW*CBp), padded apart).  reflect / replicate padding of Q is supported (pad_mode).
  * ---------------------------------------------------------------------------------------------------------- */
 typedef struct dl_wgrad_desc {
     int32_t N, Hp, Wp, CAp, p_pstride;   /* P: coarse grid                                   */
     int32_t Hq, Wq, CBp, q_pstride;      /* Q: gathered grid                                 */
-    int32_t KH, KW, step, pad, pad_mode;
+    int32_t KH, KW, step, pad, pad_mode; /* pad_mode DL_PAD_*: how Q is extended by `pad`; reflect and replicate only for step == 1 layers, any other value is
+                                            an error.  Replicate takes wgrad_w4_kernel on the ResnetBlock shape like zero padding (border inside the kernel) */
     int32_t CA, CB;                      /* real channel counts of the fp32 gradient tensor  */
     int32_t dtype;                       /* dtype of P and Q                                 */
     int32_t prec;
@@ -312,6 +315,15 @@ int dl_conv_narrow_forward_x3(const void *x, int N, int H, int W, int Ci, int x_
  * was copied from (dst: [N, H, W, Cp]).  pad < min(H, W) as for nn.ReflectionPad2d.  fp32 accumulation, fixed order. */
 int dl_reflect_fold(int dtype, const void *src, int src_pstride, void *dst, int dst_pstride, int N, int H, int W, int pad, int Cp,
                     void *stream);
+/* Backward of nn.ReplicationPad2d(pad) in front of a padding=0 Conv2d (ResnetBlock with padding_type='replicate', networks.py:482-483 / 499-500), used like
+ * dl_reflect_fold behind the pad-0 data-gradient plan:  dst[n,h,w,:] = sum of src[n,hp,wp,:] over every position of the padded extent (H+2*pad) x (W+2*pad)
+ * whose clamp (min(max(hp-pad,0),H-1), min(max(wp-pad,0),W-1)) is (h,w) -- an interior pixel receives one term, an edge pixel pad+1, a corner (pad+1)^2.
+ * Any pad >= 1 is legal for any H, W >= 1 (a clamp needs no second pixel).  fp32 accumulation in a fixed order (rows outer, columns inner); DL_F32 or DL_BF16.
+ * dtype | DL_FOLD_SRC_F32: src is fp32 whatever dst's type -- the raw accumulators of dl_conv_forward(raw_out) -- so that a 16-bit data gradient is rounded
+ * ONCE, at dst: with a 16-bit src an edge pixel would sum up to (pad+1)^2 values that were each rounded already (error u * sum |term|, not u * |result|). */
+#define DL_FOLD_SRC_F32 0x100
+int dl_replicate_fold(int dtype, const void *src, int src_pstride, void *dst, int dst_pstride, int N, int H, int W, int pad, int Cp,
+                      void *stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Normalisation (networks.py:25-44: BatchNorm2d on batch statistics / InstanceNorm2d; eps 1e-5, biased variance)

@@ -1,6 +1,9 @@
 """Time the ResnetBlock conv shape (3x3 256->256 @ 8x128x128) in isolation: forward, data gradient, weight gradient.
 
-  python tools/conv_time.py [precision=fp32] [which=fwd,dgrad,wgrad]
+  python tools/conv_time.py [precision=fp32] [which=fwd,dgrad,wgrad] [border=zero]
+border = zero | reflect | replicate: the padding mode of the forward and of the weight gradient (the data gradient of a non-zero border is the pad-0 plan
+over the padded extent + a fold: not timed here).  which = ab: SAME-PROCESS A/B of `border` against zero padding -- alternating blocks zero, border, zero,
+border, ... of the forward and of the weight gradient; prints every block, the two means and the spread between the zero-padding blocks.
 Environment switches of the library (DL_X3_VAR, DL_CONV_ABLATE, DL_NO_X3_GLDS, ...) are read by the C side at first use, so every variant is a
 separate process (tools/gpu_r03_var.sh loops over them)."""
 import os, sys, torch
@@ -12,7 +15,9 @@ be = ops.impl()
 prec = Precision.get(sys.argv[1] if len(sys.argv) > 1 else 'fp32')
 which = (sys.argv[2] if len(sys.argv) > 2 else 'fwd,dgrad,wgrad').split(',')
 DEV = 'cuda'
-spec = ConvSpec('conv', 256, 256, 3, 1, 1)
+BORDER = sys.argv[3] if len(sys.argv) > 3 else 'zero'
+PADS = {'zero': L.PAD_ZERO, 'reflect': L.PAD_REFLECT, 'replicate': L.PAD_REPLICATE}
+spec = ConvSpec('conv', 256, 256, 3, 1, 1, PADS[BORDER])
 data = os.environ.get('TIME_DATA', 'randn')       # randn | zero | bf16 (fp32 values that are exactly representable in bf16): DVFS / data-dependence probe
 w = torch.randn(256, 256, 3, 3, device=DEV) * 0.02
 x = torch.randn(8, 128, 128, 256, device=DEV).to(prec.dtype)
@@ -35,7 +40,7 @@ if SPLIT:
     x, dy = _split_copy(x), _split_copy(dy)
 KW = {'in_split': True} if SPLIT else {}
 pf = ops.PackedWeights(spec.forward_plan(), DEV, prec.prec == L.PREC_BF16X3); be.pack_weights(pf, w)
-pd = ops.PackedWeights(spec.dgrad_plan(), DEV, prec.prec == L.PREC_BF16X3); be.pack_weights(pd, w)
+pd = ops.PackedWeights(ConvSpec('conv', 256, 256, 3, 1, 1).dgrad_plan(), DEV, prec.prec == L.PREC_BF16X3); be.pack_weights(pd, w)
 grad = torch.zeros(256, 256, 3, 3, device=DEV)
 
 
@@ -67,7 +72,21 @@ if 'fwdstats' in which:          # the forward as the step launches it: bias + f
 if 'dgrad' in which:
     res['dgrad_us'] = timeit(lambda: be.conv_forward(pd, dy, out, 128, 128, None, 0, 0, prec.prec, **KW))
 if 'wgrad' in which:
-    res['wgrad_us'] = timeit(lambda: be.conv_wgrad(dy, x, grad, 3, 1, 1, L.PAD_ZERO, 0, 0, prec.prec, False))
+    res['wgrad_us'] = timeit(lambda: be.conv_wgrad(dy, x, grad, 3, 1, 1, PADS[BORDER], 0, 0, prec.prec, False))
+if 'ab' in which:
+    pz = ops.PackedWeights(ConvSpec('conv', 256, 256, 3, 1, 1).forward_plan(), DEV, prec.prec == L.PREC_BF16X3); be.pack_weights(pz, w)
+    blocks = int(os.environ.get('TIME_BLOCKS', '4'))
+    for what, run in (('fwd', lambda packed, pm: be.conv_forward(packed, x, out, 128, 128, None, 0, 0, prec.prec, **KW)),
+                      ('wgrad', lambda packed, pm: be.conv_wgrad(dy, x, grad, 3, 1, 1, pm, 0, 0, prec.prec, False))):
+        t = {'zero': [], BORDER: []}
+        for _ in range(blocks):
+            for tag, packed in (('zero', pz), (BORDER, pf)):
+                t[tag].append(round(timeit(lambda: run(packed, PADS[tag])), 2))
+                if what == 'fwd':
+                    res[f'ab_fwd_kernel_{tag}'] = be.last_conv_kernel
+        res[f'ab_{what}_blocks_us'] = t
+        res[f'ab_{what}_mean_us'] = {k: round(sum(v) / len(v), 2) for k, v in t.items()}
+        res[f'ab_{what}_zero_spread_us'] = round(max(t['zero']) - min(t['zero']), 2)
 gf = 2 * 8 * 128 * 128 * 256 * 2304 / 1e9
-print(prec.name, {k: (round(v, 1) if isinstance(v, float) else v) for k, v in res.items()}, {k.replace('_us', '_tf'): round(gf / v * 1e3, 1) for k, v in res.items() if k.endswith('_us')},
-      {k: v for k, v in os.environ.items() if k.startswith('DL_') or k == 'TIME_DATA'})
+print(prec.name, {k: (round(v, 1) if isinstance(v, float) else v) for k, v in res.items()}, {k.replace('_us', '_tf'): round(gf / v * 1e3, 1) for k, v in res.items() if k.endswith('_us') and isinstance(v, float)},
+      {k: v for k, v in os.environ.items() if k.startswith('DL_') or k == 'TIME_DATA'}, {'border': BORDER})
