@@ -21,7 +21,7 @@ NORM_INSTANCE, NORM_BATCH = 0, 1
 LOSS_BCE_LOGITS, LOSS_MSE, LOSS_SMOOTH_L1, LOSS_L1, LOSS_LINEAR = 0, 1, 2, 3, 4
 MAX_TAPS, MAX_PHASES = 64, 4
 WGRAD_MULTI_MAX = 24
-DL_VERSION = 117
+DL_VERSION = 118
 
 i32 = C.c_int32
 
@@ -69,6 +69,10 @@ class NormDesc(C.Structure):
                 ('dtype', i32), ('scope', i32), ('act', i32), ('eps', C.c_float), ('momentum', C.c_float), ('ext_nchunks', i32)]
 
 
+class DropoutDesc(C.Structure):      # dl_dropout_desc
+    _fields_ = [('p', C.c_float), ('seed', C.c_uint64), ('seed_dev', C.c_void_p), ('call_index', C.c_uint32)]
+
+
 _vp, _f, _i, _i64 = C.c_void_p, C.c_float, C.c_int, C.c_int64
 
 # every symbol include/deepliif_hip.h declares: name -> (restype, argtypes)
@@ -113,9 +117,13 @@ SIGNATURES = {
     'dl_norm_ws_floats': (C.c_size_t, [C.POINTER(NormDesc)]),
     'dl_norm_forward': (_i, [C.POINTER(NormDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'dl_norm_backward': (_i, [C.POINTER(NormDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
+    'dl_norm_forward_dropout': (_i, [C.POINTER(NormDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(DropoutDesc)]),
+    'dl_norm_backward_dropout': (_i, [C.POINTER(NormDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp,
+                                      C.POINTER(DropoutDesc)]),
     'dl_act_forward': (_i, [_i, _i, _vp, _i, _vp, _i, _i64, _i, _vp]),
     'dl_act_backward': (_i, [_i, _i, _vp, _i, _vp, _i, _vp, _i, _i64, _i, _vp]),
     'dl_dropout': (_i, [_i, _vp, _i, _vp, _i, _i64, _i, _f, C.c_uint64, _vp]),
+    'dl_dropout_dev': (_i, [_i, _vp, _i, _vp, _i, _i64, _i, C.POINTER(DropoutDesc), _vp]),
     'dl_axpby': (_i, [_i, _f, _vp, _i, _f, _vp, _i, _vp, _i, _i64, _i, _vp]),
     'dl_gate_forward': (_i, [_i, _vp, _i, _vp, _i, _vp, _i, _i64, _i, _vp]),
     'dl_gate_backward': (_i, [_i, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _i64, _i, _vp]),

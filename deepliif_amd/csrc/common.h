@@ -226,6 +226,41 @@ __device__ __forceinline__ float act_grad_from_output(int act, float y) {
     }
 }
 
+// ---- dropout keep mask (dl_dropout, and the norm kernels that apply it in registers): a counter-based hash of (folded seed, index of the
+// element in the DENSE [npix][Cp] tensor) -- a function of pixel and channel alone, never of a stride
+__device__ __forceinline__ uint32_t hash32(uint32_t x) {
+    x ^= x >> 16; x *= 0x7feb352dU; x ^= x >> 15; x *= 0x846ca68bU; x ^= x >> 16;
+    return x;
+}
+__host__ __device__ __forceinline__ uint32_t dropout_fold_seed(uint64_t s) { return (uint32_t)s ^ (uint32_t)(s >> 32) * 0x85ebca6bU; }
+// What a kernel needs of a dl_dropout_desc.  seed_dev == NULL: `seed` is the effective seed already; otherwise it is the call index, and the
+// kernel adds the step seed it reads from the device (a captured graph replays fixed arguments; the step seed is data).
+struct DropArgs {
+    const uint64_t *seed_dev;
+    uint64_t seed;
+    uint32_t thresh;
+    float scale;
+};
+__device__ __forceinline__ uint32_t dropout_seed32(const DropArgs &a) {
+    const uint64_t s = ((a.seed_dev ? *a.seed_dev : 0ull) + a.seed) & 0x7fffffffffffffffull;
+    return dropout_fold_seed(s);
+}
+// host side: the kernel arguments of a descriptor (p in [0, 1) was checked by the caller)
+static inline DropArgs dl_drop_args(const dl_dropout_desc *d) {
+    DropArgs a;
+    a.seed_dev = d->seed_dev;
+    a.seed = d->seed_dev ? (uint64_t)d->call_index : ((d->seed + d->call_index) & 0x7fffffffffffffffull);
+    a.thresh = (uint32_t)((double)d->p * 4294967296.0);
+    a.scale = 1.f / (1.f - d->p);
+    return a;
+}
+// v[k] = keep ? v[k] * scale : 0 for the 8 consecutive elements that start at dense index e8 (a multiple of 8)
+__device__ __forceinline__ void dropout8(float (&v)[8], size_t e8, uint32_t s32, uint32_t thresh, float scale) {
+    const uint32_t base = hash32((uint32_t)e8 ^ (uint32_t)(e8 >> 32) * 0x9e3779b9U ^ s32);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) v[k] = (hash32(base + 0x9e3779b9U * (uint32_t)(k + 1)) >= thresh) ? v[k] * scale : 0.f;
+}
+
 // wave64 butterfly sum
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

@@ -608,10 +608,7 @@ extern "C" int dl_adam_step_dev(float *param, const float *grad, float *exp_avg,
 // ------------------------------------------------------------------------------------------- dropout
 // nn.Dropout(0.5) of ResnetBlock / UnetSkipConnectionBlock (networks.py:493-494, 604-605): y = x * keep / (1 - p).  The keep mask
 // is a counter-based hash of (seed, element index), so the backward pass regenerates it from the same seed instead of storing it.
-__device__ __forceinline__ uint32_t hash32(uint32_t x) {
-    x ^= x >> 16; x *= 0x7feb352dU; x ^= x >> 15; x *= 0x846ca68bU; x ^= x >> 16;
-    return x;
-}
+// (hash32 / dropout8: common.h -- the norm kernels draw the same mask in registers, dl_norm_forward_dropout / dl_norm_backward_dropout)
 template <typename T>
 __global__ void __launch_bounds__(256) dropout_kernel(const T *x, int x_ps, T *y, int y_ps, size_t npix, int Cp, uint32_t seed, uint32_t thresh,
                                                       float scale) {
@@ -622,9 +619,7 @@ __global__ void __launch_bounds__(256) dropout_kernel(const T *x, int x_ps, T *y
         const int c0 = (int)(i % cvec) * 8;
         float v[8];
         Vec8<T>::load(x + p * x_ps + c0, v);
-        const uint32_t base = hash32((uint32_t)(i * 8) ^ (uint32_t)((i * 8) >> 32) * 0x9e3779b9U ^ seed);
-#pragma unroll
-        for (int k = 0; k < 8; ++k) v[k] = (hash32(base + 0x9e3779b9U * (uint32_t)(k + 1)) >= thresh) ? v[k] * scale : 0.f;
+        dropout8(v, i * 8, seed, thresh, scale);
         Vec8<T>::store(y + p * y_ps + c0, v);
     }
 }
@@ -633,10 +628,38 @@ extern "C" int dl_dropout(int dtype, const void *x, int x_ps, void *y, int y_ps,
     if (!x || !y || Cp % 8 || x_ps % 8 || y_ps % 8 || !(p >= 0.f && p < 1.f)) DL_FAIL("dl_dropout: bad argument");
     const size_t total = (size_t)npix * (Cp / 8);
     const uint32_t thresh = (uint32_t)((double)p * 4294967296.0);
-    const uint32_t s32 = (uint32_t)seed ^ (uint32_t)(seed >> 32) * 0x85ebca6bU;
+    const uint32_t s32 = dropout_fold_seed(seed);
     if (dtype == DL_F32) hipLaunchKernelGGL(dropout_kernel<float>, dim3(EW_BLOCKS(total)), dim3(256), 0, stream, (const float *)x, x_ps, (float *)y, y_ps, (size_t)npix, Cp, s32, thresh, 1.f / (1.f - p));
     else hipLaunchKernelGGL(dropout_kernel<bf16_t>, dim3(EW_BLOCKS(total)), dim3(256), 0, stream, (const bf16_t *)x, x_ps, (bf16_t *)y, y_ps, (size_t)npix, Cp, s32, thresh, 1.f / (1.f - p));
     DL_CHECK_LAUNCH("dl_dropout");
+    return 0;
+}
+
+// The same pass with the seed of a dl_dropout_desc: the effective seed may live in device memory (drop->seed_dev), where a captured graph of the
+// training step finds a new one at every replay.  Same mask as dl_dropout(seed = effective seed).
+template <typename T>
+__global__ void __launch_bounds__(256) dropout_dev_kernel(const T *x, int x_ps, T *y, int y_ps, size_t npix, int Cp, DropArgs da) {
+    const int cvec = Cp / 8;
+    const size_t total = npix * cvec;
+    const uint32_t s32 = dropout_seed32(da);
+    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+        const size_t p = i / cvec;
+        const int c0 = (int)(i % cvec) * 8;
+        float v[8];
+        Vec8<T>::load(x + p * x_ps + c0, v);
+        dropout8(v, i * 8, s32, da.thresh, da.scale);
+        Vec8<T>::store(y + p * y_ps + c0, v);
+    }
+}
+extern "C" int dl_dropout_dev(int dtype, const void *x, int x_ps, void *y, int y_ps, int64_t npix, int Cp, const dl_dropout_desc *drop, void *stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (!x || !y || !drop || Cp % 8 || x_ps % 8 || y_ps % 8 || npix <= 0 || !(drop->p >= 0.f && drop->p < 1.f)) DL_FAIL("dl_dropout_dev: bad argument");
+    if (dtype != DL_F32 && dtype != DL_BF16) DL_FAIL("dl_dropout_dev: dtype %d", dtype);
+    const size_t total = (size_t)npix * (Cp / 8);
+    const DropArgs da = dl_drop_args(drop);
+    if (dtype == DL_F32) hipLaunchKernelGGL(dropout_dev_kernel<float>, dim3(EW_BLOCKS(total)), dim3(256), 0, stream, (const float *)x, x_ps, (float *)y, y_ps, (size_t)npix, Cp, da);
+    else hipLaunchKernelGGL(dropout_dev_kernel<bf16_t>, dim3(EW_BLOCKS(total)), dim3(256), 0, stream, (const bf16_t *)x, x_ps, (bf16_t *)y, y_ps, (size_t)npix, Cp, da);
+    DL_CHECK_LAUNCH("dl_dropout_dev");
     return 0;
 }
 

@@ -53,16 +53,28 @@ template <typename T> __device__ __forceinline__ void nld_pd(const T *p, float (
 template <typename T> __device__ __forceinline__ void nld_a(const T *p, float (&v)[8]) { if constexpr ((DL_NORM_NT & 2) != 0) Vec8<T>::load_nt(p, v); else Vec8<T>::load(p, v); }
 template <typename T> __device__ __forceinline__ void nst_a(T *p, const float (&v)[8]) { if constexpr ((DL_NORM_NT & 1) != 0) Vec8<T>::store_nt(p, v); else Vec8<T>::store(p, v); }
 
+// Dropout applied in registers (dl_norm_forward_dropout / dl_norm_backward_dropout): a compile-time flag of the three streaming kernels, spelled as a
+// trailing parameter pack `Drop` that is either empty or {DropArgs}.  With the empty pack a kernel has the parameter list, and the code, it had before the
+// flag existed (the overloads below are empty); with DropArgs it masks and scales in registers.
+__device__ __forceinline__ uint32_t drop_seed() { return 0u; }
+__device__ __forceinline__ uint32_t drop_seed(const DropArgs &da) { return dropout_seed32(da); }
+// mask + scale of the 8 channels c0.. of pixel `pix` (index over the whole batch): the element index is the one of the dense [npix][Cp] tensor
+__device__ __forceinline__ void drop8(float (&)[8], uint32_t, size_t, int, int) {}
+__device__ __forceinline__ void drop8(float (&v)[8], uint32_t s32, size_t pix, int Cp, int c0, const DropArgs &da) {
+    dropout8(v, pix * (size_t)Cp + c0, s32, da.thresh, da.scale);
+}
+
 // MODE 0: forward statistics  (s1 = sum y, s2 = sum y^2)
 // MODE 1: backward reductions (s1 = sum dn, s2 = sum dn * xhat), dn = dz * act'(y*scale+shift)
 // ACT (the activation fused behind the norm) is a TEMPLATE parameter of the three streaming kernels: as a runtime argument its
 // if / else-if ladder (with tanhf in one arm) was compiled to real branches per element -- ~100 scalar branches per loop iteration,
 // which held these kernels at 4.0-4.5 TB/s while the branch-free axpby kernel streams the same tensors at 6.6 TB/s.
-template <typename T, int MODE, int ACT>
+template <typename T, int MODE, int ACT, typename... Drop>
 __global__ void __launch_bounds__(256) norm_partial_kernel(const T *y, int y_ps, const T *dz, int dz_ps, NormGeom g,
                                                            const float *mean, const float *rstd, const float *scale, const float *shift,
-                                                           float *part) {
+                                                           float *part, Drop... da) {
     constexpr int act = ACT;
+    const uint32_t s32 = drop_seed(da...);
     __shared__ float red[256 * 17];
     const int tid = threadIdx.x;
     const int n = blockIdx.x / g.nchunks, chunk = blockIdx.x % g.nchunks;
@@ -95,6 +107,7 @@ __global__ void __launch_bounds__(256) norm_partial_kernel(const T *y, int y_ps,
                 } else {
                     float d[8];
                     nld_pd<T>(dz + pix * dz_ps + c0, d);
+                    if constexpr (sizeof...(Drop) != 0) drop8(d, s32, pix, g.Cp, c0, da...);
 #pragma unroll
                     for (int i = 0; i < 8; ++i) {
                         const float nv = v[i] * sc[i] + sh[i];
@@ -232,10 +245,11 @@ __global__ void __launch_bounds__(256) norm_fwd_finalize_kernel(const float *sum
 
 // z = act(y*scale + shift) (+res): each thread owns one 8-channel column of one image (per-channel constants live in
 // registers) and walks down the pixels; grid = (pixel blocks, N)
-template <typename T, int ACT>
+template <typename T, int ACT, typename... Drop>
 __global__ void __launch_bounds__(256) norm_apply_kernel(const T *y, int y_ps, const float *scale, const float *shift, const T *res, int r_ps,
-                                                         T *z, int z_ps, NormGeom g, float *split, int split_ps) {
+                                                         T *z, int z_ps, NormGeom g, float *split, int split_ps, Drop... da) {
     constexpr int act = ACT;
+    const uint32_t s32 = drop_seed(da...);
     const int cvec = g.Cp / 8;
     const int n = blockIdx.y;
     for (int cbase = 0; cbase < cvec; cbase += 256) {
@@ -267,6 +281,7 @@ __global__ void __launch_bounds__(256) norm_apply_kernel(const T *y, int y_ps, c
 #pragma unroll
                     for (int k = 0; k < 8; ++k) v[u][k] += r[u][k];
                 }
+                if constexpr (sizeof...(Drop) != 0) drop8(v[u], s32, (size_t)n * g.HW + p + u * pstep, g.Cp, c0, da...);
                 if (z) nst_a<T>(z + ((size_t)n * g.HW + p + u * pstep) * z_ps + c0, v[u]);       // z == NULL: only the split copy is wanted
                 if (split) store_split8(split + ((size_t)n * g.HW + p + u * pstep) * split_ps + c0, v[u]);
             }
@@ -283,6 +298,7 @@ __global__ void __launch_bounds__(256) norm_apply_kernel(const T *y, int y_ps, c
 #pragma unroll
                 for (int k = 0; k < 8; ++k) v[k] += r[k];
             }
+            if constexpr (sizeof...(Drop) != 0) drop8(v, s32, pix, g.Cp, c0, da...);
             if (z) nst_a<T>(z + pix * z_ps + c0, v);
             if (split) store_split8(split + pix * split_ps + c0, v);
         }
@@ -311,12 +327,13 @@ __global__ void __launch_bounds__(256) norm_bwd_finalize_kernel(const float *sum
 }
 
 // dy = gamma*rstd*(dn - c1 - xhat*c2): same thread->column ownership as norm_apply_kernel
-template <typename T, int ACT>
+template <typename T, int ACT, typename... Drop>
 __global__ void __launch_bounds__(256) norm_bwd_apply_kernel(const T *dz, int dz_ps, const T *y, int y_ps, const float *gamma,
                                                              const float *mean, const float *rstd, const float *scale, const float *shift,
                                                              const float *c1, const float *c2, T *dy, int dy_ps, NormGeom g,
-                                                             float *bpart, float *split, int split_ps) {
+                                                             float *bpart, float *split, int split_ps, Drop... da) {
     constexpr int act = ACT;
+    const uint32_t s32 = drop_seed(da...);
     __shared__ float bred[256 * 9];
     const int cvec = g.Cp / 8;
     const int n = blockIdx.y;
@@ -352,6 +369,7 @@ __global__ void __launch_bounds__(256) norm_bwd_apply_kernel(const T *dz, int dz
 #pragma unroll
             for (int u = 0; u < U; ++u) {
                 float o[8];
+                if constexpr (sizeof...(Drop) != 0) drop8(d[u], s32, (size_t)n * g.HW + p + u * pstep, g.Cp, c0, da...);
                 const float (&V)[8] = v[u];
                 const float (&D)[8] = d[u];
 #pragma unroll
@@ -374,6 +392,7 @@ __global__ void __launch_bounds__(256) norm_bwd_apply_kernel(const T *dz, int dz
             float V[8], D[8], o[8];
             nld_a<T>(y + pix * y_ps + c0, V);
             nld_a<T>(dz + pix * dz_ps + c0, D);
+            if constexpr (sizeof...(Drop) != 0) drop8(D, s32, pix, g.Cp, c0, da...);
 #pragma unroll
             for (int k = 0; k < 8; ++k) {
                 const float nv = V[k] * sc[k] + sh[k];
@@ -469,11 +488,19 @@ static int check_desc(const dl_norm_desc *d, const char *who) {
     return 0;
 }
 
-extern "C" int dl_norm_forward(const dl_norm_desc *d, const void *y, const float *gamma, const float *beta,
-                               float *running_mean, float *running_var, float *mean, float *rstd, float *scale, float *shift,
-                               const void *residual, void *z, float *ws, void *z_split, void *stream_) {
+static int check_drop(const dl_dropout_desc *drop, const char *who) {
+    if (!drop) DL_FAIL("%s: null dropout descriptor", who);
+    if (!(drop->p >= 0.f && drop->p < 1.f)) DL_FAIL("%s: dropout p = %g is outside [0, 1)", who, (double)drop->p);
+    return 0;
+}
+
+// drop == NULL: dl_norm_forward; otherwise dl_norm_forward_dropout
+static int norm_forward_impl(const dl_norm_desc *d, const void *y, const float *gamma, const float *beta,
+                             float *running_mean, float *running_var, float *mean, float *rstd, float *scale, float *shift,
+                             const void *residual, void *z, float *ws, void *z_split, void *stream_, const dl_dropout_desc *drop) {
     hipStream_t stream = (hipStream_t)stream_;
     if (check_desc(d, "dl_norm_forward")) return -1;
+    if (drop && residual) DL_FAIL("dl_norm_forward_dropout: a residual together with dropout is not supported (dropout(act(norm(y))) + residual has no call site)");
     if (z_split && d->dtype != DL_F32) DL_FAIL("dl_norm_forward: the split copy belongs to the fp32 (strict) policy");
     if (!y || !mean || !rstd || !scale || !shift || !ws) DL_FAIL("dl_norm_forward: null argument");
     if (!z && !z_split) DL_FAIL("dl_norm_forward: z may only be NULL when z_split receives the result");
@@ -506,18 +533,44 @@ extern "C" int dl_norm_forward(const dl_norm_desc *d, const void *y, const float
                                                   scale, shift, (const float *)residual, d->r_pstride, (float *)z, d->z_pstride, g, (float *)z_split, d->Cp)
 #define DL_LAUNCH_APPLY_BF16(A) hipLaunchKernelGGL((norm_apply_kernel<bf16_t, A>), blocks, dim3(256), 0, stream, (const bf16_t *)y, d->y_pstride, \
                                                    scale, shift, (const bf16_t *)residual, d->r_pstride, (bf16_t *)z, d->z_pstride, g, (float *)nullptr, 0)
-    if (d->dtype == DL_F32) { DL_NORM_ACT_SWITCH(d->act, DL_LAUNCH_APPLY_F32) }
+#define DL_LAUNCH_APPLY_DROP_F32(A) hipLaunchKernelGGL((norm_apply_kernel<float, A>), blocks, dim3(256), 0, stream, (const float *)y, d->y_pstride, \
+                                                       scale, shift, (const float *)nullptr, d->r_pstride, (float *)z, d->z_pstride, g, (float *)z_split, d->Cp, da)
+#define DL_LAUNCH_APPLY_DROP_BF16(A) hipLaunchKernelGGL((norm_apply_kernel<bf16_t, A>), blocks, dim3(256), 0, stream, (const bf16_t *)y, d->y_pstride, \
+                                                        scale, shift, (const bf16_t *)nullptr, d->r_pstride, (bf16_t *)z, d->z_pstride, g, (float *)nullptr, 0, da)
+    if (drop) {
+        const DropArgs da = dl_drop_args(drop);
+        if (d->dtype == DL_F32) { DL_NORM_ACT_SWITCH(d->act, DL_LAUNCH_APPLY_DROP_F32) }
+        else { DL_NORM_ACT_SWITCH(d->act, DL_LAUNCH_APPLY_DROP_BF16) }
+    }
+    else if (d->dtype == DL_F32) { DL_NORM_ACT_SWITCH(d->act, DL_LAUNCH_APPLY_F32) }
     else { DL_NORM_ACT_SWITCH(d->act, DL_LAUNCH_APPLY_BF16) }
     DL_CHECK_LAUNCH("dl_norm_forward(apply)");
     return 0;
 }
 
-extern "C" int dl_norm_backward(const dl_norm_desc *d, const void *dz, const void *y, const float *gamma,
-                                const float *mean, const float *rstd, const float *scale, const float *shift,
-                                void *dy, float *dgamma, float *dbeta, int accumulate_affine, float *dy_chansum, float *ws, void *dy_split,
-                                void *stream_) {
+extern "C" int dl_norm_forward(const dl_norm_desc *d, const void *y, const float *gamma, const float *beta,
+                               float *running_mean, float *running_var, float *mean, float *rstd, float *scale, float *shift,
+                               const void *residual, void *z, float *ws, void *z_split, void *stream_) {
+    return norm_forward_impl(d, y, gamma, beta, running_mean, running_var, mean, rstd, scale, shift, residual, z, ws, z_split, stream_, nullptr);
+}
+
+extern "C" int dl_norm_forward_dropout(const dl_norm_desc *d, const void *y, const float *gamma, const float *beta,
+                                       float *running_mean, float *running_var, float *mean, float *rstd, float *scale, float *shift,
+                                       const void *residual, void *z, float *ws, void *z_split, void *stream_, const dl_dropout_desc *drop) {
+    if (check_drop(drop, "dl_norm_forward_dropout")) return -1;
+    return norm_forward_impl(d, y, gamma, beta, running_mean, running_var, mean, rstd, scale, shift, residual, z, ws, z_split, stream_, drop);
+}
+
+// drop == NULL: dl_norm_backward; otherwise dl_norm_backward_dropout
+static int norm_backward_impl(const dl_norm_desc *d, const void *dz, const void *y, const float *gamma,
+                              const float *mean, const float *rstd, const float *scale, const float *shift,
+                              void *dy, float *dgamma, float *dbeta, int accumulate_affine, float *dy_chansum, float *ws, void *dy_split,
+                              void *stream_, const dl_dropout_desc *drop) {
     hipStream_t stream = (hipStream_t)stream_;
     if (check_desc(d, "dl_norm_backward")) return -1;
+    if (drop && d->ext_nchunks > 0)
+        DL_FAIL("dl_norm_backward_dropout: ext_nchunks = %d together with dropout is not supported (partials produced by a convolution were computed "
+                "from the unmasked gradient)", d->ext_nchunks);
     if (dy_split && d->dtype != DL_F32) DL_FAIL("dl_norm_backward: the split copy belongs to the fp32 (strict) policy");
     if (!dz || !y || !mean || !rstd || !scale || !shift || !ws) DL_FAIL("dl_norm_backward: null argument");
     if (!dy && !dy_split) DL_FAIL("dl_norm_backward: dy may only be NULL when dy_split receives the result");
@@ -535,7 +588,17 @@ extern "C" int dl_norm_backward(const dl_norm_desc *d, const void *dz, const voi
                                                  d->y_pstride, (const float *)dz, dz_ps, g, mean, rstd, scale, shift, part)
 #define DL_LAUNCH_BRED_BF16(A) hipLaunchKernelGGL((norm_partial_kernel<bf16_t, 1, A>), dim3(pblocks), dim3(256), 0, stream, (const bf16_t *)y, \
                                                   d->y_pstride, (const bf16_t *)dz, dz_ps, g, mean, rstd, scale, shift, part)
-    if (ext) { /* partials are in place */ }
+#define DL_LAUNCH_BRED_DROP_F32(A) hipLaunchKernelGGL((norm_partial_kernel<float, 1, A>), dim3(pblocks), dim3(256), 0, stream, (const float *)y, \
+                                                      d->y_pstride, (const float *)dz, dz_ps, g, mean, rstd, scale, shift, part, da)
+#define DL_LAUNCH_BRED_DROP_BF16(A) hipLaunchKernelGGL((norm_partial_kernel<bf16_t, 1, A>), dim3(pblocks), dim3(256), 0, stream, (const bf16_t *)y, \
+                                                       d->y_pstride, (const bf16_t *)dz, dz_ps, g, mean, rstd, scale, shift, part, da)
+    DropArgs da = {};
+    if (drop) da = dl_drop_args(drop);
+    if (drop) {
+        if (d->dtype == DL_F32) { DL_NORM_ACT_SWITCH(d->act, DL_LAUNCH_BRED_DROP_F32) }
+        else { DL_NORM_ACT_SWITCH(d->act, DL_LAUNCH_BRED_DROP_BF16) }
+    }
+    else if (ext) { /* partials are in place */ }
     else if (d->dtype == DL_F32) { DL_NORM_ACT_SWITCH(d->act, DL_LAUNCH_BRED_F32) }
     else { DL_NORM_ACT_SWITCH(d->act, DL_LAUNCH_BRED_BF16) }
     DL_CHECK_LAUNCH("dl_norm_backward(reduce)");
@@ -557,7 +620,17 @@ extern "C" int dl_norm_backward(const dl_norm_desc *d, const void *dz, const voi
 #define DL_LAUNCH_BAPPLY_BF16(A) hipLaunchKernelGGL((norm_bwd_apply_kernel<bf16_t, A>), blocks, dim3(256), 0, stream, (const bf16_t *)dz, dz_ps, \
                                                     (const bf16_t *)y, d->y_pstride, gamma, mean, rstd, scale, shift, c1, c2, (bf16_t *)dy, dy_ps, g, bpart, \
                                                     (float *)nullptr, 0)
-    if (d->dtype == DL_F32) { DL_NORM_ACT_SWITCH(d->act, DL_LAUNCH_BAPPLY_F32) }
+#define DL_LAUNCH_BAPPLY_DROP_F32(A) hipLaunchKernelGGL((norm_bwd_apply_kernel<float, A>), blocks, dim3(256), 0, stream, (const float *)dz, dz_ps, \
+                                                        (const float *)y, d->y_pstride, gamma, mean, rstd, scale, shift, c1, c2, (float *)dy, dy_ps, g, bpart, \
+                                                        (float *)dy_split, d->Cp, da)
+#define DL_LAUNCH_BAPPLY_DROP_BF16(A) hipLaunchKernelGGL((norm_bwd_apply_kernel<bf16_t, A>), blocks, dim3(256), 0, stream, (const bf16_t *)dz, dz_ps, \
+                                                         (const bf16_t *)y, d->y_pstride, gamma, mean, rstd, scale, shift, c1, c2, (bf16_t *)dy, dy_ps, g, bpart, \
+                                                         (float *)nullptr, 0, da)
+    if (drop) {
+        if (d->dtype == DL_F32) { DL_NORM_ACT_SWITCH(d->act, DL_LAUNCH_BAPPLY_DROP_F32) }
+        else { DL_NORM_ACT_SWITCH(d->act, DL_LAUNCH_BAPPLY_DROP_BF16) }
+    }
+    else if (d->dtype == DL_F32) { DL_NORM_ACT_SWITCH(d->act, DL_LAUNCH_BAPPLY_F32) }
     else { DL_NORM_ACT_SWITCH(d->act, DL_LAUNCH_BAPPLY_BF16) }
     DL_CHECK_LAUNCH("dl_norm_backward(apply)");
     if (dy_chansum) {
@@ -565,4 +638,19 @@ extern "C" int dl_norm_backward(const dl_norm_desc *d, const void *dz, const voi
         DL_CHECK_LAUNCH("dl_norm_backward(bias sum)");
     }
     return 0;
+}
+
+extern "C" int dl_norm_backward(const dl_norm_desc *d, const void *dz, const void *y, const float *gamma,
+                                const float *mean, const float *rstd, const float *scale, const float *shift,
+                                void *dy, float *dgamma, float *dbeta, int accumulate_affine, float *dy_chansum, float *ws, void *dy_split,
+                                void *stream_) {
+    return norm_backward_impl(d, dz, y, gamma, mean, rstd, scale, shift, dy, dgamma, dbeta, accumulate_affine, dy_chansum, ws, dy_split, stream_, nullptr);
+}
+
+extern "C" int dl_norm_backward_dropout(const dl_norm_desc *d, const void *dz, const void *y, const float *gamma,
+                                        const float *mean, const float *rstd, const float *scale, const float *shift,
+                                        void *dy, float *dgamma, float *dbeta, int accumulate_affine, float *dy_chansum, float *ws, void *dy_split,
+                                        void *stream_, const dl_dropout_desc *drop) {
+    if (check_drop(drop, "dl_norm_backward_dropout")) return -1;
+    return norm_backward_impl(d, dz, y, gamma, mean, rstd, scale, shift, dy, dgamma, dbeta, accumulate_affine, dy_chansum, ws, dy_split, stream_, drop);
 }

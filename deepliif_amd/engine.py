@@ -767,11 +767,21 @@ def conv(ctx: Ctx, x: Act, layer: ConvLayer, act: int = L.ACT_NONE, in_act: int 
 
 
 def norm_act(ctx: Ctx, y: Act, norm: Optional[NormLayer], act: int = L.ACT_NONE, residual: Optional[Act] = None,
-             out: Optional[torch.Tensor] = None, sole_reader: Optional['ConvLayer'] = None) -> Act:
+             out: Optional[torch.Tensor] = None, sole_reader: Optional['ConvLayer'] = None, dropout: float = 0.0) -> Act:
     """z = act(norm(y)) (+ residual).  norm None = identity norm (norm='none').
     sole_reader: the caller's promise that the result is read by conv(ctx, z, sole_reader) and by NOTHING else (no residual use, no dropout, no
-    concat, not returned): under the strict policy the fp32 values are then not stored when that conv reads the split copy everywhere."""
+    concat, not returned): under the strict policy the fp32 values are then not stored when that conv reads the split copy everywhere.
+    dropout > 0: z = dropout(act(norm(y))), nn.Dropout(dropout) in training mode behind the norm.  A backend with `supports_fused_dropout` applies the
+    mask inside the norm kernels, forward and backward (one pass over the tensor each way instead of two); any other one runs norm_act followed by
+    dropout().  Either way the site draws ONE seed of the sequence (_dropout_site), so both routes drop the same units."""
     be = ops.impl()
+    drop_site = None
+    if dropout > 0.0:
+        assert residual is None and sole_reader is None, 'dropout(act(norm(y))) takes no residual and is not a split-only tensor'
+        if not (ctx.training and norm is not None and getattr(be, 'supports_fused_dropout', False)):
+            assert out is None, 'the unfused route cannot place its result: run norm_act, dropout and the copy separately'
+            return _dropout_fn(ctx, norm_act(ctx, y, norm, act), dropout)
+        drop_site = _dropout_site(dropout)
     own_out = out is None
     if out is None:
         out = empty_like_act(y.t)
@@ -818,6 +828,8 @@ def norm_act(ctx: Ctx, y: Act, norm: Optional[NormLayer], act: int = L.ACT_NONE,
         kwf['z_split'] = zs
     if split_only:
         kwf['store_z'] = False
+    if drop_site is not None:
+        kwf['dropout'] = drop_site
     stats = be.norm_forward(y.t, out, norm.C, scope, act, gamma, beta, rm, rv, momentum, residual.t if residual is not None else None,
                             ext_nchunks=ext, **kwf)
     z = Act(out, y.C, needs)
@@ -825,7 +837,8 @@ def norm_act(ctx: Ctx, y: Act, norm: Optional[NormLayer], act: int = L.ACT_NONE,
     z.values_stored = not split_only
     if not needs:
         return z
-    if residual is None and act in (L.ACT_NONE, L.ACT_RELU, L.ACT_LRELU) and y.t.dtype == torch.bfloat16 and y.needs_grad:
+    # (with dropout the consumer's data gradient is not yet the gradient of act(norm(y)): its store epilogue must not produce this norm's reductions)
+    if residual is None and drop_site is None and act in (L.ACT_NONE, L.ACT_RELU, L.ACT_LRELU) and y.t.dtype == torch.bfloat16 and y.needs_grad:
         z.bn_ctx = (y.t, stats, act)
 
     track_affine = m is not None and m.weight.requires_grad
@@ -845,7 +858,7 @@ def norm_act(ctx: Ctx, y: Act, norm: Optional[NormLayer], act: int = L.ACT_NONE,
         gs, z.grad_stats = z.grad_stats, None
         if g is None:
             return
-        ext_b = gs[0] if (gs is not None and gs[1] == be.norm_ws_token()) else 0
+        ext_b = gs[0] if (gs is not None and gs[1] == be.norm_ws_token() and drop_site is None) else 0
         if residual is not None and residual.needs_grad:
             residual.add_grad(g)
         affine = m is not None and m.weight.requires_grad
@@ -866,6 +879,8 @@ def norm_act(ctx: Ctx, y: Act, norm: Optional[NormLayer], act: int = L.ACT_NONE,
                 kw['dy_split'] = dys
             if split_only:
                 kw['store_dy'] = False
+            if drop_site is not None:
+                kw['dropout'] = drop_site            # the forward call's (seed, call index): the same mask on the gradient
             be.norm_backward(g, y.t, dy, stats, norm.C, scope, act, gamma, m.weight.grad if affine else None, m.bias.grad if affine else None,
                              y.bias_grad if fuse_bias else None, ext_nchunks=ext_b, **kw)
             if fuse_bias:
@@ -887,16 +902,107 @@ def _rank() -> int:
     return dist.get_rank() if dist.is_available() and dist.is_initialized() else 0
 
 
+def _seed_base() -> int:
+    """what the dropout seeds of this process count up from: the seed of site number k (k = _DROPOUT_COUNTER after its tick) is (base + k) mod 2^63.
+    The rank is mixed in: replicas seeded identically (parameters are broadcast anyway) must not drop the same units on different tiles"""
+    return int(torch.initial_seed()) * 1000003 + 7919 * _rank()
+
+
+_SEED_MASK = 2 ** 63 - 1
+_SEED_RING = 4
+_DEVICE_SEEDS = [None]          # the DropoutSeeds of the step that is running with device seeds (models.StepGraph(capture_dropout=True)), or None
+
+
+class DropoutSeeds:
+    """Dropout seeds a captured training step can replay.  A captured graph replays fixed kernel arguments, so a seed passed by value would repeat the
+    masks of the captured step for ever.  Here the step's seed lives in device memory (`dev`, one int64) and every site of the step passes that
+    pointer and its position in the step (call_index = 1..J); the kernels add the two.  Before a step the host stages
+        base = (_seed_base() + _DROPOUT_COUNTER) mod 2^63,
+    after it _DROPOUT_COUNTER += J: site j draws base + j, exactly the seed the host-seed route (_dropout_site) gives it -- a step draws the same
+    masks either way, and eager steps, warm-up steps and replays can be mixed freely.
+    Staging goes through a RING of pinned buffers, each with the event of its last copy (as optim.FusedAdam's scalars): the asynchronous copy reads
+    the pinned memory when it EXECUTES, and the host may run steps ahead of the GPU; a slot is rewritten only after its previous copy has run."""
+
+    def __init__(self, device, ring: int = _SEED_RING, event_factory=None):
+        device = torch.device(device)
+        cuda = device.type == 'cuda'
+        if event_factory is None and cuda:
+            event_factory = torch.cuda.Event
+        self.dev = torch.zeros(1, dtype=torch.int64, device=device)
+        self._ring = [(torch.zeros(1, dtype=torch.int64).pin_memory() if cuda else torch.zeros(1, dtype=torch.int64),
+                       event_factory() if event_factory is not None else None) for _ in range(ring)]
+        self._slot, self._used = 0, [False] * ring
+        self.index = 0                  # sites served in the open step
+        self.base = None                # the base seed last staged
+
+    def stage(self) -> int:
+        """put this step's base seed where the kernels read it (outside any captured region, before the step is launched)"""
+        slot = self._slot
+        host, ev = self._ring[slot]
+        if ev is not None and self._used[slot]:
+            ev.synchronize()             # the copy that last read this slot has executed (a no-op unless the host is a ring's length ahead)
+        self.base = (_seed_base() + _DROPOUT_COUNTER[0]) & _SEED_MASK
+        host[0] = self.base
+        self.dev.copy_(host, non_blocking=True)
+        if ev is not None:
+            ev.record()
+        self._used[slot] = True
+        self._slot = (slot + 1) % len(self._ring)
+        return self.base
+
+    def begin_step(self):
+        """stage the seed and route every dropout site to it until end_step() / cancel_step()"""
+        assert _DEVICE_SEEDS[0] is None, 'a step with device seeds is already open'
+        self.stage()
+        self.index = 0
+        _DEVICE_SEEDS[0] = self
+
+    def next_index(self) -> int:
+        self.index += 1
+        return self.index
+
+    def end_step(self) -> int:
+        """close the step: the seed sequence moves past the J sites it served; returns J"""
+        assert _DEVICE_SEEDS[0] is self
+        _DEVICE_SEEDS[0] = None
+        _DROPOUT_COUNTER[0] += self.index
+        return self.index
+
+    def cancel_step(self):
+        """close a step whose launches never ran (a failed capture): the seed sequence stays where it was before begin_step()"""
+        if _DEVICE_SEEDS[0] is self:
+            _DEVICE_SEEDS[0] = None
+        self.index = 0
+
+    def replay_step(self, sites: int):
+        """a replay of a captured step with `sites` dropout sites: stage its seed, move the sequence past it"""
+        assert _DEVICE_SEEDS[0] is None
+        self.stage()
+        _DROPOUT_COUNTER[0] += sites
+
+
+def _dropout_site(p: float):
+    """(p, seed, seed_dev, call_index) of the next dropout site (ops.HipBackend: dl_dropout_desc): one tick of the seed sequence, host seed or -- inside
+    a step opened by DropoutSeeds.begin_step() -- the step's device seed and the site's index"""
+    ds = _DEVICE_SEEDS[0]
+    if ds is not None:
+        return (p, 0, ds.dev, ds.next_index())
+    _DROPOUT_COUNTER[0] += 1
+    return (p, (_seed_base() + _DROPOUT_COUNTER[0]) & _SEED_MASK, None, 0)
+
+
 def dropout(ctx: Ctx, x: Act, p: float, in_place: bool = False) -> Act:
     """nn.Dropout(p) in training mode.  The mask is a function of a per-call seed (torch's CPU RNG seeds the stream, so
     torch.manual_seed() makes runs repeatable); backward re-applies the same mask to the gradient."""
     be = ops.impl()
-    _DROPOUT_COUNTER[0] += 1
-    # the rank is mixed in: replicas seeded identically (parameters are broadcast anyway) must not drop the same units on different tiles
-    seed = (int(torch.initial_seed()) * 1000003 + 7919 * _rank() + _DROPOUT_COUNTER[0]) & (2 ** 63 - 1)
+    site = _dropout_site(p)
+    seed = site[1]
     assert not (in_place and ctx.tape is not None and x.needs_grad), 'in-place dropout would let the gradient through unmasked: use in_place=False when training'
     out = x.t if in_place else empty_like_act(x.t)
-    be.dropout(x.t, out, p, seed)
+    if site[2] is not None:              # the step runs with device seeds: the same pass reading its seed from the device
+        be.dropout_dev(x.t, out, site)
+    else:
+        be.dropout(x.t, out, p, seed)
     needs = ctx.tape is not None and x.needs_grad
     z = x if in_place else Act(out, x.C, needs)
     if needs and not in_place:
@@ -906,10 +1012,16 @@ def dropout(ctx: Ctx, x: Act, p: float, in_place: bool = False) -> Act:
             if g is None:
                 return
             dx = empty_like_act(g)
-            be.dropout(g, dx, p, seed)
+            if site[2] is not None:
+                be.dropout_dev(g, dx, site)
+            else:
+                be.dropout(g, dx, p, seed)
             x.add_grad(dx)
         ctx.tape.record(backward)
     return z
+
+
+_dropout_fn = dropout            # (norm_act's `dropout` argument hides the function's name there)
 
 
 def concat_channels(ctx: Ctx, parts: List[Act], out: Optional[torch.Tensor] = None) -> Act:

@@ -107,15 +107,19 @@ class StepGraph:
       * the batch: copied into persistent device tensors (`static batch`) before every step; set_input(static batch) -- the NCHW -> engine layout
         conversions -- is part of the captured region;
       * Adam's scalars (scheduler learning rate, bias corrections): optim.FusedAdam graph mode, refreshed by prepare_step() outside the graph.
+      * with capture_dropout=True, the dropout seed: every step (warm-up, capture, replay) runs with DEVICE seeds (engine.DropoutSeeds) -- the kernels
+        read the step's base seed from device memory and add the site's index, step() stages the base seed next to prepare_step().  The number of
+        sites J is counted in the warm-up steps and must be the same at capture.  The masks are those of the eager step with host seeds.
     step(batch): the first `warmup` calls run eagerly (first-use initialisation: function attributes, pack tables, workspaces), the next one
     captures, every later one replays.  Results are bit-identical to the eager step (tests/test_gpu_graph.py: reference trajectories).
     Falls back to eager for good, saying why, when the step cannot be captured: data-parallel exchange active (collectives are launched from tape
-    callbacks on RCCL's own streams), dropout in training mode (the mask seed is a kernel argument), an optimizer other than FusedAdam, a model
-    class with host-side randomness (CycleGAN's ImagePool)."""
+    callbacks on RCCL's own streams), dropout in training mode unless capture_dropout is set (the mask seed is a kernel argument), an optimizer
+    other than FusedAdam, a model class with host-side randomness (CycleGAN's ImagePool)."""
 
-    def __init__(self, model, warmup: int = 2):
+    def __init__(self, model, warmup: int = 2, capture_dropout: bool = False):
         self.model, self.warmup = model, max(2, warmup)      # two eager steps: the second one still creates state (the repack table sees the data-gradient images)
         self.calls, self.graph, self.static, self.why_eager = 0, None, None, None
+        self.seeds, self.sites = None, None                  # engine.DropoutSeeds and the dropout sites per step (capture_dropout)
         from . import distributed as D
         from .optim import FusedAdam
         if D.active():
@@ -126,7 +130,7 @@ class StepGraph:
             self.why_eager = f'{type(model).__name__} has host-side state per step'
         elif not all(isinstance(o, FusedAdam) for o in model.optimizers):
             self.why_eager = 'an optimizer other than FusedAdam'
-        elif any(isinstance(m, torch.nn.Dropout) and m.training for _, net in model._nets() for m in net.modules()):
+        elif not capture_dropout and any(isinstance(m, torch.nn.Dropout) and m.training for _, net in model._nets() for m in net.modules()):
             self.why_eager = 'dropout is active (its seed is a kernel argument)'
         elif any(getattr(net, 'spectral_norm', False) for _, net in model._nets()):
             # the host picks a generation per forward call and keeps per-call state (engine.SpectralSet): not a fixed launch sequence
@@ -136,6 +140,8 @@ class StepGraph:
         else:
             for o in model.optimizers:
                 o.enable_graph_mode()
+            if capture_dropout:
+                self.seeds = E.DropoutSeeds(model.device)
 
     def _to_static(self, batch):
         dev = self.model.device
@@ -193,23 +199,41 @@ class StepGraph:
         for o in m.optimizers:
             o.prepare_step()
         self.calls += 1
+        seeds = self.seeds
         if self.graph is not None:
+            if seeds is not None:
+                seeds.replay_step(self.sites)
             self.graph.replay()
         elif self.calls <= self.warmup:
-            m.set_input(static)
-            m.optimize_parameters()
+            if seeds is not None:
+                seeds.begin_step()
+            try:
+                m.set_input(static)
+                m.optimize_parameters()
+            except BaseException:
+                if seeds is not None:
+                    seeds.cancel_step()
+                raise
+            if seeds is not None:
+                sites = seeds.end_step()
+                assert self.sites in (None, sites), f'the step drew {sites} dropout masks, the step before it {self.sites}: not a fixed launch sequence'
+                self.sites = sites
         else:
             torch.cuda.synchronize()
             g = torch.cuda.CUDAGraph()
             wst = ops.WS._thread_state()
             try:
                 wst['capturing'] = True             # (ops.Workspace._state: the capture stream keeps this thread's scratch state)
+                if seeds is not None:
+                    seeds.begin_step()              # staged here, outside the captured region: the replay below is this step
                 try:
                     with torch.cuda.graph(g):
                         m.set_input(static)
                         m.optimize_parameters()
                 finally:
                     wst['capturing'] = False
+                if seeds is not None and seeds.index != self.sites:
+                    raise RuntimeError(f'the captured step draws {seeds.index} dropout masks, the warm-up steps drew {self.sites}')
             except Exception as exc:
                 # something on the step path still needs the host during the step (e.g. a table that is only complete after another eager step:
                 # the batched weight-repack table grows while data-gradient images appear).  Nothing was executed; run this step -- and all later
@@ -221,6 +245,8 @@ class StepGraph:
                 abandon = getattr(ops.impl(), 'wgrad_abandon', None)
                 if abandon is not None:
                     abandon()                        # weight gradients recorded by the aborted pass never ran: nothing of them may be reduced later
+                if seeds is not None:
+                    seeds.cancel_step()              # no mask of the aborted pass was drawn: the eager step below takes the same seeds, from the host
                 for o in m.optimizers:               # back to the scalar-argument Adam kernel (same arithmetic); prepare_step() had counted this step
                     o.hyper_dev, o._prepared = None, False
                     o.step_count -= 1
@@ -228,6 +254,8 @@ class StepGraph:
                 m.set_input(static)
                 m.optimize_parameters()
                 return
+            if seeds is not None:
+                seeds.end_step()
             self.graph = g
             self._ws_generation = ops.Workspace.realloc_generation
             g.replay()                  # capture records, it does not execute: this step's work

@@ -258,9 +258,8 @@ class ResnetGenerator(EngineNet):
             (c1, n1), (c2, n2) = ent
             drop = blk.use_dropout and blk.training
             # without dropout the block's inner activation is read by its second conv only: the strict policy keeps just its split copy
-            r = E.norm_act(ctx, E.conv(ctx, h, c1, stats=n1 is not None), n1, L.ACT_RELU, sole_reader=None if drop else c2)
-            if drop:                                   # nn.Dropout(0.5) after the first norm+ReLU (networks.py:493-494)
-                r = E.dropout(ctx, r, 0.5)
+            # nn.Dropout(0.5) after the first norm+ReLU (networks.py:493-494): applied inside the norm kernels where the backend can (engine.norm_act)
+            r = E.norm_act(ctx, E.conv(ctx, h, c1, stats=n1 is not None), n1, L.ACT_RELU, sole_reader=None if drop else c2, dropout=0.5 if drop else 0.0)
             # the last block's output is read by the first up-convolution only (every other one is the next block's residual as well)
             last_out = b['up'][0][0] if (ib == nblk - 1 and self.upsample == 'convtranspose') else None
             h = E.norm_act(ctx, E.conv(ctx, r, c2, stats=n2 is not None), n2, L.ACT_NONE, residual=h, sole_reader=last_out)
@@ -383,8 +382,14 @@ class UnetGenerator(EngineNet):
             second = cat[..., cout:]
             y = E.conv(ctx, u_in, l['up'], in_act=L.ACT_RELU, stats=True)
             drop = l['block'].use_dropout and l['block'].training      # nn.Dropout(0.5) on the block output (networks.py:604-605)
+            if drop and ctx.training and l['upnorm'] is not None and getattr(E.ops.impl(), 'supports_fused_dropout', False):
+                # one pass: the norm kernel drops in registers and stores straight into the concat slice (the mask depends on pixel and channel only,
+                # not on the slice's stride); its backward masks the slice of the concat gradient as it loads it
+                u = E.norm_act(ctx, y, l['upnorm'], L.ACT_NONE, out=second, dropout=0.5)
+                u_in = _JoinedAct(cat, 2 * cout, firsts[d], u, ctx)
+                continue
             u = E.norm_act(ctx, y, l['upnorm'], L.ACT_NONE, out=None if drop else second)
-            if drop:
+            if drop:                                                   # three passes: norm apply, dropout, copy into the concat buffer
                 ud = E.dropout(ctx, u, 0.5)
                 ops_impl = E.ops.impl()
                 ops_impl.axpby(1.0, ud.t, 0.0, None, second)           # place the dropped tensor into the concat buffer

@@ -666,10 +666,26 @@ class HipBackend:
         d.eps, d.momentum = 1e-5, momentum
         return d
 
-    def norm_forward(self, y, z, C_real, scope, act, gamma, beta, running_mean, running_var, momentum, residual, ext_nchunks=0, z_split=None, store_z=True):
+    # dropout applied inside the norm kernels (norm_forward / norm_backward(dropout=...)): engine.norm_act takes the one-pass route when this is set
+    supports_fused_dropout = True
+
+    @staticmethod
+    def _dropout_desc(dropout):
+        """(p, seed, seed_dev, call_index) -> dl_dropout_desc; seed_dev: None or a one-element int64 device tensor holding the step seed"""
+        p, seed, seed_dev, call_index = dropout
+        dd = L.DropoutDesc()
+        dd.p, dd.seed, dd.call_index = float(p), int(seed) & (2 ** 64 - 1), int(call_index)
+        if seed_dev is not None:
+            assert seed_dev.is_cuda and seed_dev.dtype == torch.int64 and seed_dev.numel() == 1
+            dd.seed_dev = seed_dev.data_ptr()
+        return dd
+
+    def norm_forward(self, y, z, C_real, scope, act, gamma, beta, running_mean, running_var, momentum, residual, ext_nchunks=0, z_split=None, store_z=True,
+                     dropout=None):
         """ext_nchunks > 0: the convolution that produced y already left its partial sums in the 'norm_ws' workspace.
         z_split (fp32 policy): dense buffer shaped like z that receives the split copy of z ([8 bf16 hi | 8 bf16 lo] per 8 channels);
-        store_z=False (needs z_split): `z` only gives the geometry, its fp32 values are NOT written"""
+        store_z=False (needs z_split): `z` only gives the geometry, its fp32 values are NOT written
+        dropout = (p, seed, seed_dev, call_index): z / z_split receive dropout(act(norm(y))) (dl_norm_forward_dropout; no residual)"""
         _need_cuda(y, z, gamma, beta, residual, z_split)
         assert store_z or z_split is not None
         assert z_split is None or (z_split.is_contiguous() and z_split.dtype == torch.float32 and z_split.shape == z.shape)
@@ -679,14 +695,20 @@ class HipBackend:
             WS.bump_norm_token()            # the stand-alone statistics pass overwrites the shared workspace
         stats = torch.empty(4, y.shape[0], y.shape[3], dtype=torch.float32, device=y.device)   # mean, rstd, scale, shift
         ws = WS.get('norm_ws', self.lib.dl_norm_ws_floats(C.byref(d)), y.device)
-        self.check(self.lib.dl_norm_forward(C.byref(d), _ptr(y), _ptr(gamma), _ptr(beta), _ptr(running_mean), _ptr(running_var),
-                                         _ptr(stats[0]), _ptr(stats[1]), _ptr(stats[2]), _ptr(stats[3]), _ptr(residual), _ptr(z) if store_z else None,
-                                         _ptr(ws), _ptr(z_split), _stream()), 'dl_norm_forward')
+        args = (C.byref(d), _ptr(y), _ptr(gamma), _ptr(beta), _ptr(running_mean), _ptr(running_var),
+                _ptr(stats[0]), _ptr(stats[1]), _ptr(stats[2]), _ptr(stats[3]), _ptr(residual), _ptr(z) if store_z else None,
+                _ptr(ws), _ptr(z_split), _stream())
+        if dropout is None:
+            self.check(self.lib.dl_norm_forward(*args), 'dl_norm_forward')
+        else:
+            self.check(self.lib.dl_norm_forward_dropout(*args, C.byref(self._dropout_desc(dropout))), 'dl_norm_forward_dropout')
         return stats
 
-    def norm_backward(self, dz, y, dy, stats, C_real, scope, act, gamma, dgamma, dbeta, dy_chansum=None, ext_nchunks=0, dy_split=None, store_dy=True):
+    def norm_backward(self, dz, y, dy, stats, C_real, scope, act, gamma, dgamma, dbeta, dy_chansum=None, ext_nchunks=0, dy_split=None, store_dy=True,
+                      dropout=None):
         """ext_nchunks > 0: the conv that produced dz already left the reductions in the 'norm_ws' workspace (conv_forward(bn=...)).
-        dy_split: see norm_forward(z_split).  store_dy=False (needs dy_split): `dy` only gives the geometry, its fp32 values are NOT written."""
+        dy_split: see norm_forward(z_split).  store_dy=False (needs dy_split): `dy` only gives the geometry, its fp32 values are NOT written.
+        dropout = the tuple the forward call took: dz is masked and scaled as it is loaded (dl_norm_backward_dropout; no ext_nchunks)."""
         _need_cuda(dz, y, dy, dy_chansum, dy_split)
         assert store_dy or dy_split is not None
         assert dy_split is None or (dy_split.is_contiguous() and dy_split.dtype == torch.float32 and dy_split.shape == dy.shape)
@@ -694,10 +716,12 @@ class HipBackend:
         d.ext_nchunks = ext_nchunks
         WS.bump_norm_token()
         ws = WS.get('norm_ws', self.lib.dl_norm_ws_floats(C.byref(d)), y.device)
-        self.check(self.lib.dl_norm_backward(C.byref(d), _ptr(dz), _ptr(y), _ptr(gamma), _ptr(stats[0]), _ptr(stats[1]), _ptr(stats[2]),
-                                          _ptr(stats[3]), _ptr(dy) if store_dy else None, _ptr(dgamma), _ptr(dbeta), 1, _ptr(dy_chansum), _ptr(ws), _ptr(dy_split),
-                                          _stream()),
-                'dl_norm_backward')
+        args = (C.byref(d), _ptr(dz), _ptr(y), _ptr(gamma), _ptr(stats[0]), _ptr(stats[1]), _ptr(stats[2]),
+                _ptr(stats[3]), _ptr(dy) if store_dy else None, _ptr(dgamma), _ptr(dbeta), 1, _ptr(dy_chansum), _ptr(ws), _ptr(dy_split), _stream())
+        if dropout is None:
+            self.check(self.lib.dl_norm_backward(*args), 'dl_norm_backward')
+        else:
+            self.check(self.lib.dl_norm_backward_dropout(*args, C.byref(self._dropout_desc(dropout))), 'dl_norm_backward_dropout')
 
     # ---- elementwise
     def act_forward(self, act, x, y):
@@ -716,6 +740,13 @@ class HipBackend:
         npix = x.shape[0] * x.shape[1] * x.shape[2]
         self.check(self.lib.dl_dropout(dl_dtype(x), _ptr(x), pstride(x), _ptr(y), pstride(y), npix, x.shape[3], float(p), int(seed) & (2 ** 64 - 1),
                                     _stream()), 'dl_dropout')
+
+    def dropout_dev(self, x, y, dropout):
+        """dropout() with the seed of a (p, seed, seed_dev, call_index) tuple: the step seed may live in device memory (engine.DropoutSeeds)"""
+        _need_cuda(x, y)
+        npix = x.shape[0] * x.shape[1] * x.shape[2]
+        self.check(self.lib.dl_dropout_dev(dl_dtype(x), _ptr(x), pstride(x), _ptr(y), pstride(y), npix, x.shape[3],
+                                        C.byref(self._dropout_desc(dropout)), _stream()), 'dl_dropout_dev')
 
     def axpby(self, alpha, a, beta, b, out):
         _need_cuda(a, b, out)

@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define DL_VERSION 117
+#define DL_VERSION 118
 
 enum { DL_F32 = 0, DL_BF16 = 1 };           /* DL_BF16 = "the 16-bit type of this library": bfloat16, or IEEE half in libdeepliif_hip_f16.so (below) */
 enum { DL_HALF_BF16 = 0, DL_HALF_FP16 = 1 };   /* dl_half_format() */
@@ -367,6 +367,33 @@ int dl_norm_backward(const dl_norm_desc *d, const void *dz, const void *y, const
                      const float *mean, const float *rstd, const float *scale, const float *shift,
                      void *dy, float *dgamma, float *dbeta, int accumulate_affine, float *dy_chansum, float *ws, void *dy_split, void *stream);
 
+/* nn.Dropout(p) in training mode applied INSIDE the norm kernels (one pass over the tensor instead of two), and the seed a captured graph can replay.
+ *   effective seed s = ((seed_dev ? *seed_dev : seed) + call_index) & (2^63 - 1), folded to 32 bits as dl_dropout folds its seed
+ *   (lo ^ hi * 0x85ebca6b; with seed_dev the kernel reads the step seed and folds it);
+ *   keep(element) = hash(s32, index of the element in the DENSE [N*H*W][Cp] tensor) >= p * 2^32 -- dl_dropout's mask for seed s.  It depends on
+ *   pixel and channel only, never on a stride: a channel-slice view of a wider buffer receives the same mask.
+ * seed_dev (may be NULL) points to ONE uint64 in device memory that the caller rewrites between steps (outside a captured graph); call_index
+ * then numbers the dropout sites of the step (1..J), so that step seed + call_index walks the same sequence host seeds would. */
+typedef struct dl_dropout_desc {
+    float p;                         /* drop probability, 0 <= p < 1; kept values are scaled by 1 / (1 - p)   */
+    uint64_t seed;                   /* host seed (ignored when seed_dev is set)                              */
+    const uint64_t *seed_dev;        /* device seed, or NULL                                                  */
+    uint32_t call_index;
+} dl_dropout_desc;
+/* dl_norm_forward with z / z_split = dropout(act(norm(y))): mask and scale are applied in registers before the one store of the apply pass (the
+ * same kernel behind a compile-time flag).  The statistics outputs are those of dl_norm_forward.  A residual is rejected (no call site needs it). */
+int dl_norm_forward_dropout(const dl_norm_desc *d, const void *y, const float *gamma, const float *beta,
+                            float *running_mean, float *running_var,
+                            float *mean, float *rstd, float *scale, float *shift,
+                            const void *residual, void *z, float *ws, void *z_split, void *stream, const dl_dropout_desc *drop);
+/* dl_norm_backward of that forward: dz is masked and scaled as it is loaded, in the reduction pass and in the apply pass, so dy, dgamma / dbeta,
+ * dy_chansum and dy_split are what dl_dropout(dz) followed by dl_norm_backward gives.  ext_nchunks > 0 is rejected: partials a convolution
+ * produced were computed from the unmasked gradient. */
+int dl_norm_backward_dropout(const dl_norm_desc *d, const void *dz, const void *y, const float *gamma,
+                             const float *mean, const float *rstd, const float *scale, const float *shift,
+                             void *dy, float *dgamma, float *dbeta, int accumulate_affine, float *dy_chansum, float *ws, void *dy_split, void *stream,
+                             const dl_dropout_desc *drop);
+
 /* ------------------------------------------------------------------------------------------------------------
  * Elementwise (networks.py nn.ReLU / nn.LeakyReLU(0.2) / nn.Tanh, torch.cat, the seg weighted sum
  * DeepLIIF_model.py:203, gradient accumulation).  All take NHWC views: (ptr, pstride, npix, Cp).
@@ -386,6 +413,8 @@ int dl_gate_backward(int dtype, const void *g, int g_pstride, const void *x, int
 /* nn.Dropout(p) in training mode (networks.py:493-494, 604-605): y = x * keep / (1-p), keep = hash(seed, element) >= p.
  * Calling it again with the same seed on the gradient reproduces the same mask (backward); y may alias x. */
 int dl_dropout(int dtype, const void *x, int x_pstride, void *y, int y_pstride, int64_t npix, int Cp, float p, uint64_t seed, void *stream);
+/* the same pass with the seed of a dl_dropout_desc (above): where no norm kernel is in front to apply the mask (norm 'none'), and as the fallback */
+int dl_dropout_dev(int dtype, const void *x, int x_pstride, void *y, int y_pstride, int64_t npix, int Cp, const dl_dropout_desc *drop, void *stream);
 /* out = alpha*a + beta*b   (b may be NULL; out may alias a or b) */
 int dl_axpby(int dtype, float alpha, const void *a, int a_pstride, float beta, const void *b, int b_pstride,
              void *out, int out_pstride, int64_t npix, int Cp, void *stream);
