@@ -1543,59 +1543,47 @@ static bool w4_enabled() {
     return !(w4 && w4[0] == '0');
 }
 
-// A replicate-padded ResnetBlock conv takes conv_gemm_w4_kernel at ANY tile count: its alternative is not the 8-phase kernel but the per-chunk
-// gather (a non-zero border never reaches the scalar-tap kernels), and one routing rule per mode keeps small and large launches of a layer on one kernel.
-static bool w4_takes_replicate(const ConvArgs &a) { return a.pad_mode == DL_PAD_REPLICATE && w4_enabled() && w4_eligible(a); }
-
-static int dispatch_tile_glds(const ConvArgs &a, hipStream_t stream) {
-    if (a.Co <= 16) return launch_conv_glds<256, 16, 32, 4, 1>(a, stream);
-    if (a.Co <= 64) return launch_conv_glds<128, 64, 64, 2, 2>(a, stream);
-    if (w4_takes_replicate(a)) return launch_conv_w4(a, stream);
-    static const bool no_big = DL_DEV_ENV("DL_NO_BIGTILE") != nullptr;
-    // 256x256x64, 8 waves (each 128 pixels x 64 channels): twice the FLOP per staged byte of the 128x128 tile; needs
-    // enough tiles to fill 256 CUs
-    if (!no_big && big_tile_fills_gpu(a.Mtot, a.Co, a.n_phase, a.splitk))
-    {
-        // "1": software-pipelined 32x32x16 kernel (+ kernel-column reuse).  Same-box A/B of the whole training step (r01,
-        // tools/ab_bench.sh): 121.7-122.0 ms vs 121.4-122.1 ms for the 8-phase kernel, 123.4-123.6 ms for the one-barrier kernel;
-        // launch time 175 vs 168 vs 183 us.  The step is power-capped (profiles/r01/clock_probe.txt), so the 8-phase kernel
-        // stays the default and this one is kept for the next tuning pass (it moves 33% fewer bytes into LDS).
-        // "1": 4 waves x (128 px x 128 ch) on v_mfma_32x32x16, kernel-column reuse, one barrier per K step (conv_w4.hip) for the ResnetBlock shape
-        if (w4_enabled() && w4_eligible(a)) return launch_conv_w4(a, stream);
-#ifdef DL_DEV_SWITCHES       // older kernels kept for same-box A/Bs and the timing-only ablations (results WRONG by construction): dev build only
-        static const char *p32 = DL_DEV_ENV("DL_CONV_P32");
-        if (p32 && p32[0] == '1' && a.Ci >= 64 && a.pad_mode == DL_PAD_ZERO && !a.k_order) {
-            static const char *ablp = DL_DEV_ENV("DL_CONV_ABLATE");
-            if (ablp && ablp[0] == '1') return dispatch_p32<1>(a, stream);
-            if (ablp && ablp[0] == '2') return dispatch_p32<2>(a, stream);
-            if (ablp && ablp[0] == '3') return dispatch_p32<3>(a, stream);
-            return dispatch_p32<0>(a, stream);
-        }
-        static const char *ph8 = DL_DEV_ENV("DL_CONV_8PH");            // "0": fall back to the one-barrier-per-step kernel
-        if (!(ph8 && ph8[0] == '0') && a.Ci >= 64 && a.pad_mode == DL_PAD_ZERO && !a.k_order) {
-            static const char *abl8 = DL_DEV_ENV("DL_CONV_ABLATE");
-            if (abl8 && abl8[0] == '1') return launch_conv_8ph<1>(a, stream);
-            if (abl8 && abl8[0] == '2') return launch_conv_8ph<2>(a, stream);
-            if (abl8 && abl8[0] == '3') return launch_conv_8ph<3>(a, stream);
-            if (abl8 && abl8[0] == '4') return launch_conv_8ph<4>(a, stream);
-            return launch_conv_8ph<0>(a, stream);
-        }
-        static const bool stag = DL_DEV_ENV("DL_CONV_STAGGER") != nullptr;
-        static const char *abl = DL_DEV_ENV("DL_CONV_ABLATE");       // "1": no DMA in the loop, "2": no LDS reads / MFMAs (timing only!)
-        if (abl && abl[0] == '1' && a.Ci >= 64 && a.pad_mode == DL_PAD_ZERO) return launch_conv_glds_impl<256, 256, 64, 2, 4, true, false, 1>(a, stream);
-        if (abl && abl[0] == '2' && a.Ci >= 64 && a.pad_mode == DL_PAD_ZERO) return launch_conv_glds_impl<256, 256, 64, 2, 4, true, false, 2>(a, stream);
-        if (abl && abl[0] == '4' && a.Ci >= 64 && a.pad_mode == DL_PAD_ZERO) return launch_conv_glds_impl<256, 256, 64, 2, 4, true, false, 4>(a, stream);
-        if (abl && abl[0] == '5' && a.Ci >= 64 && a.pad_mode == DL_PAD_ZERO) return launch_conv_glds_impl<256, 256, 64, 2, 4, true, false, 5>(a, stream);
-        if (stag && a.Ci >= 64 && a.pad_mode == DL_PAD_ZERO) return launch_conv_glds_impl<256, 256, 64, 2, 4, true, true>(a, stream);
-#else
-        if (a.Ci >= 64 && a.pad_mode == DL_PAD_ZERO && !a.k_order) return launch_conv_8ph<0>(a, stream);
+// ---- leaves of the launch switch (conv_forward_impl): the kernel is already chosen (conv_route); the dev build picks among its timing variants here.
+// The older big-tile kernels stay for same-box A/Bs, their ablations (results WRONG by construction) for tools/ablate.sh: dev build only.
+static int launch_conv_8ph_variant(const ConvArgs &a, hipStream_t stream) {
+#ifdef DL_DEV_SWITCHES
+    static const char *abl8 = DL_DEV_ENV("DL_CONV_ABLATE");
+    if (abl8 && abl8[0] == '1') return launch_conv_8ph<1>(a, stream);
+    if (abl8 && abl8[0] == '2') return launch_conv_8ph<2>(a, stream);
+    if (abl8 && abl8[0] == '3') return launch_conv_8ph<3>(a, stream);
+    if (abl8 && abl8[0] == '4') return launch_conv_8ph<4>(a, stream);
 #endif
-        return launch_conv_glds<256, 256, 64, 2, 4>(a, stream);
-    }
-    // (r06 experiment, dev build: a 256 x 128 tile -- 8 waves of 64 px x 64 ch, 85 flop per staged byte instead of 64 -- on the PatchGAN's c2 / c3 layers:
-    // 84.3 -> 82.6 us, 64.8 -> 63.9 us: the 128 x 128 tile is not bound by the bytes it stages; removed)
-    return launch_conv_glds<128, 128, 64, 2, 2>(a, stream);
+    return launch_conv_8ph<0>(a, stream);
 }
+
+#ifdef DL_DEV_SWITCHES
+// DL_CONV_P32=1: the software-pipelined 32x32x16 kernel (+ kernel-column reuse).  Same-box A/B of the whole training step (r01, tools/ab_bench.sh):
+// 121.7-122.0 ms vs 121.4-122.1 ms for the 8-phase kernel, 123.4-123.6 ms for the one-barrier kernel; launch time 175 vs 168 vs 183 us.  The step is
+// power-capped (profiles/r01/clock_probe.txt), so the 8-phase kernel stayed the default and this one is kept for the next tuning pass (it moves 33% fewer
+// bytes into LDS).
+static int launch_conv_p32_variant(const ConvArgs &a, hipStream_t stream) {
+    static const char *ablp = DL_DEV_ENV("DL_CONV_ABLATE");
+    if (ablp && ablp[0] == '1') return dispatch_p32<1>(a, stream);
+    if (ablp && ablp[0] == '2') return dispatch_p32<2>(a, stream);
+    if (ablp && ablp[0] == '3') return dispatch_p32<3>(a, stream);
+    return dispatch_p32<0>(a, stream);
+}
+#endif
+
+// 256x256x64, 8 waves (each 128 pixels x 64 channels): twice the FLOP per staged byte of the 128x128 tile
+static int launch_conv_glds_256_variant(const ConvArgs &a, hipStream_t stream) {
+#ifdef DL_DEV_SWITCHES
+    static const bool stag = DL_DEV_ENV("DL_CONV_STAGGER") != nullptr;
+    static const char *abl = DL_DEV_ENV("DL_CONV_ABLATE");       // "1": no DMA in the loop, "2": no LDS reads / MFMAs (timing only!)
+    if (abl && abl[0] == '1' && a.Ci >= 64 && a.pad_mode == DL_PAD_ZERO) return launch_conv_glds_impl<256, 256, 64, 2, 4, true, false, 1>(a, stream);
+    if (abl && abl[0] == '2' && a.Ci >= 64 && a.pad_mode == DL_PAD_ZERO) return launch_conv_glds_impl<256, 256, 64, 2, 4, true, false, 2>(a, stream);
+    if (abl && abl[0] == '4' && a.Ci >= 64 && a.pad_mode == DL_PAD_ZERO) return launch_conv_glds_impl<256, 256, 64, 2, 4, true, false, 4>(a, stream);
+    if (abl && abl[0] == '5' && a.Ci >= 64 && a.pad_mode == DL_PAD_ZERO) return launch_conv_glds_impl<256, 256, 64, 2, 4, true, false, 5>(a, stream);
+    if (stag && a.Ci >= 64 && a.pad_mode == DL_PAD_ZERO) return launch_conv_glds_impl<256, 256, 64, 2, 4, true, true>(a, stream);
+#endif
+    return launch_conv_glds<256, 256, 64, 2, 4>(a, stream);
+}
+
 
 // out[p][c] = act(bias[c] + sum_ks slab[ks][p][c]), fixed summation order (deterministic)
 template <typename TOut>
@@ -1644,6 +1632,7 @@ static int launch_conv(const ConvArgs &a0, hipStream_t stream) {
     return 0;
 }
 
+// conv_gemm_kernel<TIn>, chosen by conv_route(): the instantiation for the layer's channel count
 template <typename TIn, typename TOut, int PREC>
 static int dispatch_tile(const ConvArgs &a, hipStream_t stream) {
     constexpr int BK = (PREC == 3) ? 32 : 64;
@@ -1666,225 +1655,174 @@ static void fill_conv_geometry(ConvArgs &a, const dl_conv_desc *d) {
     a.Mtot = d->N * d->Hq * d->Wq;
 }
 
-// does dl_conv_forward send this descriptor to the fused four-phase kernel (conv_s2f.hip)?  DL_CONV_S2F=0: keep the 4-phase gather GEMM (A/B)
-static bool s2f_applies(const dl_conv_desc *d) {
-    const char *env = dl_switch(DL_SW_CONV_S2F);
-    static const bool no_glds = DL_DEV_ENV("DL_NO_GLDS") != nullptr;
-    if ((env && env[0] == '0') || no_glds || d->in_dtype != DL_BF16 || d->prec != DL_PREC_BF16 || d->in_act != DL_ACT_NONE || d->n_phase != 4) return false;
+// THE routing of dl_conv_forward and its siblings: one value per kernel they can launch (per name dl_conv_kernel_name reports), chosen in ONE place, conv_route().
+// The launch (conv_forward_impl), the name (dl_conv_kernel_name), the tile height behind the statistics chunk counts (dl_conv_stats_chunks,
+// dl_conv_bnstats_chunks) and dl_conv_add_supported all read that one decision, so they cannot drift apart; a new kernel is one enum value, one row of
+// g_routes, one rule in conv_route() and one arm of the launch switch.  First the special kernels, then the tile family (bf16 direct-to-LDS, register-staged
+// gather, strict direct-to-LDS).
+enum ConvRoute {
+    ROUTE_DOT_FWD, ROUTE_DOT_DGRAD, ROUTE_C4, ROUTE_D1, ROUTE_D1G, ROUTE_C4_X3, ROUTE_S2U, ROUTE_S2F, ROUTE_S2F_X3, ROUTE_S2D,
+    ROUTE_W4, ROUTE_8PH, ROUTE_GLDS_256x16, ROUTE_GLDS_128x64, ROUTE_GLDS_128x128, ROUTE_GLDS_256x256,
+#ifdef DL_DEV_SWITCHES
+    ROUTE_P32,
+#endif
+    ROUTE_GATHER_BF16, ROUTE_GATHER_F32,
+    ROUTE_W4X3, ROUTE_8PH_X3, ROUTE_X3_256x16, ROUTE_X3_256x32, ROUTE_X3_128x64, ROUTE_X3_128x128,
+    ROUTE_COUNT
+};
+// name: as rocprofv3 prints the kernel, without template noise.  bm: pixels per tile of the tile-family kernels that can fuse statistics (one chunk per tile
+// and phase); 0 for the special kernels, which count their own chunks (route_stats_chunks), and for conv_gemm_kernel, which has no fused statistics.
+static const struct { const char *name; int bm; } g_routes[] = {
+    {"conv_dot_fwd_kernel", 0}, {"conv_dot_dgrad_kernel", 0}, {"conv_c4_patch_kernel", 0}, {"conv_d1_kernel", 0}, {"conv_d1g_kernel", 0},
+    {"conv_c4_patch_x3_kernel", 0}, {"conv_s2u_kernel", 0}, {"conv_s2f_kernel", 0}, {"conv_s2f_x3_kernel", 0}, {"conv_s2d_kernel", 0},
+    {"conv_gemm_w4_kernel", 256}, {"conv_gemm_8ph_kernel", 256}, {"conv_gemm_glds_kernel<256,16,32>", 256}, {"conv_gemm_glds_kernel<128,64,64>", 128},
+    {"conv_gemm_glds_kernel<128,128,64>", 128}, {"conv_gemm_glds_kernel<256,256,64>", 256},
+#ifdef DL_DEV_SWITCHES
+    {"conv_gemm_p32_kernel", 256},
+#endif
+    {"conv_gemm_kernel<bf16>", 0}, {"conv_gemm_kernel<f32>", 0},
+    {"conv_gemm_w4x3_kernel", 256}, {"conv_gemm_8ph_x3_kernel", 256}, {"conv_gemm_glds_x3_kernel<256,16>", 256}, {"conv_gemm_glds_x3_kernel<256,32>", 256},
+    {"conv_gemm_glds_x3_kernel<128,64>", 128}, {"conv_gemm_glds_x3_kernel<128,128>", 128},
+};
+static_assert(sizeof(g_routes) / sizeof(*g_routes) == ROUTE_COUNT, "one row of g_routes per ConvRoute, in the order of the enum");
+
+static bool route_is_special(ConvRoute r) { return r < ROUTE_W4; }
+static bool route_is_x3_tile(ConvRoute r) { return r >= ROUTE_W4X3; }
+
+// the descriptor's geometry as the *_eligible() predicates read it: nothing but geometry (no pointers, no per-call facts), filled ONCE per decision
+static ConvArgs conv_geometry(const dl_conv_desc *d) {
+    ConvArgs g;
+    memset(&g, 0, sizeof(g));
+    fill_conv_geometry(g, d);
+    return g;
+}
+
+static bool switch_is_0(int id) { const char *v = dl_switch(id); return v && v[0] == '0'; }
+
+// The only place that orders the rules.  It decides on the DESCRIPTOR alone -- g is conv_geometry(d); a bias is d->bias_n > 0 (conv_forward_impl brings the
+// pointer in line with that) -- plus the three per-call facts the descriptor cannot carry: fused norm-backward reductions (dl_conv_forward_bnstats), fused
+// statistics (stats_part), a fused addend (dl_conv_forward_add).  g leaves as it came (two rules lend it a pointer whose presence alone is tested).
+static ConvRoute conv_route(const dl_conv_desc *d, ConvArgs &g, bool bn, bool stats, bool add) {
+    static const bool no_glds = DL_DEV_ENV("DL_NO_GLDS") != nullptr;          // A/B switch for profiling the two staging paths
     static const bool epi_old = DL_DEV_ENV("DL_OLD_EPILOGUE") != nullptr;
-    if (epi_old) return false;
-    ConvArgs a;
-    memset(&a, 0, sizeof(a));
-    fill_conv_geometry(a, d);
-    return s2f_eligible(a);
-}
-
-// does dl_conv_forward send this descriptor to the one-channel dot-product kernels (conv_dot.hip: the PatchGAN's prediction layer)?  0 = no, 1 = forward,
-// 2 = data gradient.  DL_CONV_DOT=0: keep the gather GEMM (A/B)
-static int dot_applies(const dl_conv_desc *d) {
-    const char *env = dl_switch(DL_SW_CONV_DOT);
-    if ((env && env[0] == '0') || d->in_dtype != DL_BF16 || d->prec != DL_PREC_BF16 || d->in_act != DL_ACT_NONE || d->n_phase != 1 || d->raw_out) return 0;
-    ConvArgs a;
-    memset(&a, 0, sizeof(a));
-    fill_conv_geometry(a, d);
-    a.bias = d->bias_n == 1 ? reinterpret_cast<const float *>(&a) : nullptr;        // (only its presence is tested)
-    if (dot_fwd_eligible(a)) return 1;
-    a.bias = nullptr;
-    if (d->ci_real == 1 && d->bias_n == 0 && dot_dgrad_eligible(a)) return 2;
-    return 0;
-}
-
-// ... or to the PatchGAN's first-layer kernel (conv_d1.hip: 8 contracted channels, k4 s2, 256-pixel output rows)?  DL_CONV_DOT=0 switches it off too (A/B)
-static bool d1_applies(const dl_conv_desc *d) {
-    const char *env = dl_switch(DL_SW_CONV_DOT);
-    static const bool epi_old = DL_DEV_ENV("DL_OLD_EPILOGUE") != nullptr;
-    if ((env && env[0] == '0') || epi_old || d->in_dtype != DL_BF16 || d->prec != DL_PREC_BF16 || d->in_act != DL_ACT_NONE || d->n_phase != 1 || d->in_step != 2 || d->Ci != 8 ||
-        d->splitk != 1)
-        return false;
-    ConvArgs a;
-    memset(&a, 0, sizeof(a));
-    fill_conv_geometry(a, d);
-    return d1_eligible(a);
-}
-
-// ... or to that layer's data-gradient kernel (conv_d1g.hip: four phases as the M dimension, 64 contracted and 8 output channels)?  DL_CONV_DOT=0: off (A/B)
-static bool d1g_applies(const dl_conv_desc *d) {
-    const char *env = dl_switch(DL_SW_CONV_DOT);
-    if ((env && env[0] == '0') || d->in_dtype != DL_BF16 || d->prec != DL_PREC_BF16 || d->in_act != DL_ACT_NONE || d->n_phase != 4 || d->Ci != 64 || d->Co != 8 || d->splitk != 1 ||
-        d->bias_n != 0)
-        return false;
-    ConvArgs a;
-    memset(&a, 0, sizeof(a));
-    fill_conv_geometry(a, d);
-    return d1g_eligible(a);
-}
-
-// does dl_conv_forward send this descriptor to the register-stationary stride-2 kernel (conv_s2d.hip: down1 forward, up2 data gradient)?
-// DL_CONV_S2D=0: keep the gather GEMM (A/B)
-static bool s2d_applies(const dl_conv_desc *d) {
-    const char *env = dl_switch(DL_SW_CONV_S2D);
-    static const bool no_glds = DL_DEV_ENV("DL_NO_GLDS") != nullptr;
-    static const bool epi_old = DL_DEV_ENV("DL_OLD_EPILOGUE") != nullptr;
-    if ((env && env[0] == '0') || no_glds || epi_old || d->in_dtype != DL_BF16 || d->prec != DL_PREC_BF16 || d->in_act != DL_ACT_NONE || d->n_phase != 1 || d->in_step != 2)
-        return false;
-    ConvArgs a;
-    memset(&a, 0, sizeof(a));
-    fill_conv_geometry(a, d);
-    return s2d_eligible(a);
-}
-
-// ... or to its mirror image for the UP direction (conv_s2u.hip: up2 forward, down1 data gradient)?  DL_CONV_S2D=0 switches both off (A/B)
-static bool s2u_applies(const dl_conv_desc *d) {
-    const char *env = dl_switch(DL_SW_CONV_S2D);
-    static const bool no_glds = DL_DEV_ENV("DL_NO_GLDS") != nullptr;
-    static const bool epi_old = DL_DEV_ENV("DL_OLD_EPILOGUE") != nullptr;
-    if ((env && env[0] == '0') || no_glds || epi_old || d->in_dtype != DL_BF16 || d->prec != DL_PREC_BF16 || d->in_act != DL_ACT_NONE || d->n_phase != 4 || d->Ci != 128)
-        return false;
-    ConvArgs a;
-    memset(&a, 0, sizeof(a));
-    fill_conv_geometry(a, d);
-    return s2u_eligible(a);
-}
-
-// ... and to its strict twin (conv_s2f_x3.hip)?  Needs the split copy of the input; DL_CONV_S2F=0 or DL_CONV_S2FX3=0: keep the 4-phase strict kernel (A/B)
-static bool s2fx3_applies(const dl_conv_desc *d) {
-    const char *env = dl_switch(DL_SW_CONV_S2F);
-    const char *env3 = dl_switch(DL_SW_CONV_S2FX3);
-    if ((env && env[0] == '0') || (env3 && env3[0] == '0') || d->in_dtype != DL_F32 || d->prec != DL_PREC_BF16X3 || d->in_act != DL_ACT_NONE || d->n_phase != 4 ||
-        !d->in_split || !x3_glds_applies(d))
-        return false;
-    ConvArgs a;
-    memset(&a, 0, sizeof(a));
-    fill_conv_geometry(a, d);
-    return s2f_x3_eligible(a);
-}
-
-// tile height (pixels) the dispatch picks for the bf16 direct-to-LDS path; 0 when that path is not taken
-static int glds_tile_bm(const dl_conv_desc *d) {
-    static const bool no_glds = DL_DEV_ENV("DL_NO_GLDS") != nullptr;
-    if (no_glds || d->in_dtype != DL_BF16 || d->prec != DL_PREC_BF16 || d->in_act != DL_ACT_NONE) return 0;
-    if (d->Co <= 16) return 256;
-    if (d->Co <= 64) return 128;
     static const bool no_big = DL_DEV_ENV("DL_NO_BIGTILE") != nullptr;
-    const int mtot = d->N * d->Hq * d->Wq;
-    if (!no_big && big_tile_fills_gpu(mtot, d->Co, d->n_phase, d->splitk)) return 256;
-    if (d->pad_mode == DL_PAD_REPLICATE) {
-        ConvArgs a;
-        memset(&a, 0, sizeof(a));
-        fill_conv_geometry(a, d);
-        if (w4_takes_replicate(a)) return 256;
-    }
-    return 128;
-}
-
-// THE routing of dl_conv_forward and its siblings: which special kernel takes this descriptor, ROUTE_TILE = none (the tile dispatch: gather GEMMs, w4, 8ph ...).
-// Both the launch (conv_forward_impl) and the name (dl_conv_kernel_name) are derived from this one function, so they cannot drift apart.  It decides on the
-// DESCRIPTOR alone (a bias is d->bias_n > 0; conv_forward_impl brings the pointer in line with that before anything else looks at it) plus the three per-call
-// facts the descriptor cannot carry: fused norm-backward reductions (dl_conv_forward_bnstats), fused statistics (stats_part), a fused addend (dl_conv_forward_add).
-enum ConvRoute { ROUTE_DOT_FWD, ROUTE_DOT_DGRAD, ROUTE_C4, ROUTE_D1, ROUTE_D1G, ROUTE_C4_X3, ROUTE_S2U, ROUTE_S2F, ROUTE_S2F_X3, ROUTE_S2D, ROUTE_TILE };
-
-static ConvRoute conv_route(const dl_conv_desc *d, bool bn, bool stats, bool add) {
     const bool plain = !bn && !stats && !add;
-    if (plain) {
-        if (const int k = dot_applies(d)) return k == 1 ? ROUTE_DOT_FWD : ROUTE_DOT_DGRAD;      // (no split-K, whatever the descriptor says: nothing to reduce)
+    const bool bf16 = d->in_dtype == DL_BF16 && d->prec == DL_PREC_BF16 && d->in_act == DL_ACT_NONE;      // what every 16-bit kernel but conv_gemm_kernel takes
+
+    // ---- the special kernels.  DL_CONV_DOT=0 / DL_CONV_S2D=0 / DL_CONV_S2F=0 / DL_CONV_S2FX3=0: keep the gather GEMM (A/B)
+    const bool patchgan = plain && bf16 && !switch_is_0(DL_SW_CONV_DOT);
+    // conv_dot.hip, the PatchGAN's prediction layer (no split-K, whatever the descriptor says: nothing to reduce)
+    if (patchgan && d->n_phase == 1 && !d->raw_out) {
+        g.bias = d->bias_n == 1 ? reinterpret_cast<const float *>(&g) : nullptr;        // (only its presence is tested)
+        const bool fwd = dot_fwd_eligible(g);
+        g.bias = nullptr;
+        if (fwd) return ROUTE_DOT_FWD;
+        if (d->ci_real == 1 && d->bias_n == 0 && dot_dgrad_eligible(g)) return ROUTE_DOT_DGRAD;
     }
     if (c4_bf16_eligible(d)) return ROUTE_C4;
-    if (plain && d1_applies(d)) return ROUTE_D1;
-    if (plain && d1g_applies(d)) return ROUTE_D1G;
+    // conv_d1.hip, the PatchGAN's first layer (8 contracted channels, k4 s2, 256-pixel output rows); conv_d1g.hip, its data gradient (no bias)
+    if (patchgan && !epi_old && d1_eligible(g)) return ROUTE_D1;
+    if (patchgan && d->bias_n == 0 && d1g_eligible(g)) return ROUTE_D1G;
     if (c4_x3_eligible(d)) return ROUTE_C4_X3;
-    if (!bn && s2u_applies(d)) return ROUTE_S2U;
-    if (!bn && s2f_applies(d)) return ROUTE_S2F;
-    if (!bn && s2fx3_applies(d)) return ROUTE_S2F_X3;
-    if (!bn && s2d_applies(d)) return ROUTE_S2D;
-    return ROUTE_TILE;
+    // conv_s2u.hip (up2 forward, down1 data gradient), conv_s2f.hip (the fused four-phase tile), its strict twin conv_s2f_x3.hip (needs the split copy of
+    // the input), conv_s2d.hip (down1 forward, up2 data gradient); none of them has the norm-backward reductions
+    const bool stride2 = !bn && bf16 && !no_glds && !epi_old;
+    if (stride2 && !switch_is_0(DL_SW_CONV_S2D) && s2u_eligible(g)) return ROUTE_S2U;
+    if (stride2 && !switch_is_0(DL_SW_CONV_S2F) && s2f_eligible(g)) return ROUTE_S2F;
+    if (!bn && !switch_is_0(DL_SW_CONV_S2F) && !switch_is_0(DL_SW_CONV_S2FX3) && x3_glds_applies(d) && s2f_x3_eligible(g)) return ROUTE_S2F_X3;
+    if (stride2 && !switch_is_0(DL_SW_CONV_S2D) && s2d_eligible(g)) return ROUTE_S2D;
+
+    // ---- the tile family, 16-bit policy on the direct-to-LDS kernels
+    if (bf16 && !no_glds) {
+        if (d->Co <= 16) return ROUTE_GLDS_256x16;
+        if (d->Co <= 64) return ROUTE_GLDS_128x64;
+        // A replicate-padded ResnetBlock conv takes conv_gemm_w4_kernel at ANY tile count: its alternative is not the 8-phase kernel but the per-chunk gather
+        // (a non-zero border never reaches the scalar-tap kernels), and one routing rule per mode keeps small and large launches of a layer on one kernel.
+        if (d->pad_mode == DL_PAD_REPLICATE && w4_enabled() && w4_eligible(g)) return ROUTE_W4;
+        // the 256 x 256 tiles need enough workgroups to fill 256 CUs.  (r06 experiment, dev build: a 256 x 128 tile -- 8 waves of 64 px x 64 ch, 85 flop per
+        // staged byte instead of 64 -- on the PatchGAN's c2 / c3 layers: 84.3 -> 82.6 us, 64.8 -> 63.9 us: the 128 x 128 tile is not bound by the bytes it
+        // stages; removed)
+        if (no_big || !big_tile_fills_gpu(g.Mtot, d->Co, d->n_phase, d->splitk)) return ROUTE_GLDS_128x128;
+        if (w4_enabled() && w4_eligible(g)) return ROUTE_W4;
+        // the 8-phase kernel decodes its taps on the scalar unit: whole 64-channel K steps inside one tap, zero padding, tap-major K order
+        static const char *korder_env = DL_DEV_ENV("DL_CONV_KORDER");
+        const bool scalar_taps = d->Ci >= 64 && d->pad_mode == DL_PAD_ZERO && !(korder_env && korder_env[0] == '1');
+#ifdef DL_DEV_SWITCHES
+        static const char *p32 = DL_DEV_ENV("DL_CONV_P32");
+        if (p32 && p32[0] == '1' && scalar_taps) return ROUTE_P32;
+        static const char *ph8 = DL_DEV_ENV("DL_CONV_8PH");            // "0": fall back to the one-barrier-per-step kernel
+        if (ph8 && ph8[0] == '0') return ROUTE_GLDS_256x256;
+#endif
+        return scalar_taps ? ROUTE_8PH : ROUTE_GLDS_256x256;
+    }
+    // ---- strict policy on the direct-to-LDS kernels (conv_x3.h)
+    if (x3_glds_applies(d)) {
+        if (x3_big_tile(d->in_act, d->pad_mode, d->Ci, g.Mtot, d->Co, d->n_phase, d->splitk)) {
+            if (!bn && w4x3_enabled()) {
+                g.w_lo = reinterpret_cast<const bf16_t *>(&g);          // (only its presence is tested)
+                const bool w4x3 = w4x3_eligible(g);
+                g.w_lo = nullptr;
+                if (w4x3) return ROUTE_W4X3;
+            }
+            return ROUTE_8PH_X3;
+        }
+        if (d->Co <= 16) return ROUTE_X3_256x16;
+        if (d->Co <= 32) return ROUTE_X3_256x32;          // the head's (co, kw)-stacked rows (21 -> 32): half the MFMAs of the 64-wide tile
+        if (d->Co <= 64) return ROUTE_X3_128x64;
+        return ROUTE_X3_128x128;
+    }
+    // ---- everything else: the register-staged gather (an input activation under the 16-bit policy, fp32 storage with bf16 products, DL_NO_X3_GLDS=1)
+    return d->in_dtype == DL_BF16 ? ROUTE_GATHER_BF16 : ROUTE_GATHER_F32;
 }
 
-// Name of the kernel a plain dl_conv_forward (no fused statistics / reductions / addend) launches for this descriptor (as rocprofv3 prints it, without template
-// noise): conv_route(), then the tile dispatch's own rules.  Lets the benchmark label its roofline line from the dispatch itself instead of a string that goes stale.
+// Name of the kernel a plain dl_conv_forward (no fused statistics / reductions / addend) launches for this descriptor: the row of g_routes that conv_route()
+// picks, i.e. the very decision the launch switches on.  Lets the benchmark label its roofline line from the dispatch itself instead of a string that goes stale.
 extern "C" const char *dl_conv_kernel_name(const dl_conv_desc *d) {
     if (!d) return "(null)";
-    switch (conv_route(d, false, false, false)) {
-    case ROUTE_DOT_FWD: return "conv_dot_fwd_kernel";
-    case ROUTE_DOT_DGRAD: return "conv_dot_dgrad_kernel";
-    case ROUTE_C4: return "conv_c4_patch_kernel";
-    case ROUTE_D1: return "conv_d1_kernel";
-    case ROUTE_D1G: return "conv_d1g_kernel";
-    case ROUTE_C4_X3: return "conv_c4_patch_x3_kernel";
-    case ROUTE_S2U: return "conv_s2u_kernel";
-    case ROUTE_S2F: return "conv_s2f_kernel";
-    case ROUTE_S2F_X3: return "conv_s2f_x3_kernel";
-    case ROUTE_S2D: return "conv_s2d_kernel";
-    case ROUTE_TILE: break;
-    }
-    const int bm = glds_tile_bm(d);
-    if (bm == 0 && x3_glds_applies(d)) {
-        if (w4x3_enabled()) {
-            ConvArgs a;
-            memset(&a, 0, sizeof(a));
-            fill_conv_geometry(a, d);
-            a.w_lo = reinterpret_cast<const bf16_t *>(&a);          // (only its presence is tested)
-            if (w4x3_eligible(a)) return "conv_gemm_w4x3_kernel";
-        }
-        return x3_kernel_name(d);
-    }
-    if (bm == 0) return (d->in_dtype == DL_BF16) ? "conv_gemm_kernel<bf16>" : "conv_gemm_kernel<f32>";
-    if (d->Co <= 16) return "conv_gemm_glds_kernel<256,16,32>";
-    if (d->Co <= 64) return "conv_gemm_glds_kernel<128,64,64>";
-    if (bm != 256) return "conv_gemm_glds_kernel<128,128,64>";
-    if (w4_enabled()) {
-        ConvArgs a;
-        memset(&a, 0, sizeof(a));
-        fill_conv_geometry(a, d);
-        if (w4_eligible(a)) return "conv_gemm_w4_kernel";
-    }
-    const bool utap = d->Ci >= 64 && d->pad_mode == DL_PAD_ZERO;
-    static const char *korder_env = DL_DEV_ENV("DL_CONV_KORDER");
-    const bool korder = korder_env && korder_env[0] == '1';
-    static const char *p32 = DL_DEV_ENV("DL_CONV_P32");
-    static const char *ph8 = DL_DEV_ENV("DL_CONV_8PH");
-    if (utap && !korder && p32 && p32[0] == '1') return "conv_gemm_p32_kernel";
-    if (utap && !korder && !(ph8 && ph8[0] == '0')) return "conv_gemm_8ph_kernel";
-    return "conv_gemm_glds_kernel<256,256,64>";
+    ConvArgs g = conv_geometry(d);
+    return g_routes[conv_route(d, g, false, false, false)].name;
 }
 
-extern "C" int dl_conv_stats_chunks(const dl_conv_desc *d) {
-    if (!d || d->splitk != 1 || d->raw_out || d->act != DL_ACT_NONE) return 0;
-    if (dot_applies(d) || d1_applies(d) || d1g_applies(d)) return 0;
-    if (c4_eligible(d)) return (d->Ho / 4) * (d->Wo / 64);          // one chunk per 4 x 64 tile
-    if (s2u_applies(d)) {                                            // one chunk per workgroup (row segment x strip of input rows)
-        ConvArgs a;
-        memset(&a, 0, sizeof(a));
-        fill_conv_geometry(a, d);
-        return s2u_stats_chunks(a);
-    }
-    if (s2f_applies(d) || s2fx3_applies(d)) {                        // one chunk per 256-pixel tile of the phase grid (all four phases summed)
-        ConvArgs a;
-        memset(&a, 0, sizeof(a));
-        fill_conv_geometry(a, d);
-        return s2f_stats_chunks(a);
-    }
-    if (s2d_applies(d)) {                                            // one chunk per workgroup (row segment x strip of output rows)
-        ConvArgs a;
-        memset(&a, 0, sizeof(a));
-        fill_conv_geometry(a, d);
-        return s2d_stats_chunks(a);
+// what every epilogue with fused statistics needs, whatever the kernel
+static bool stats_fusable(const dl_conv_desc *d) { return d->splitk == 1 && !d->raw_out && d->act == DL_ACT_NONE; }
+
+// chunks of fused statistics per image that the kernel of route r writes for this descriptor, 0 = none
+static int route_stats_chunks(ConvRoute r, const dl_conv_desc *d, const ConvArgs &g) {
+    if (!stats_fusable(d)) return 0;
+    switch (r) {
+    case ROUTE_C4: case ROUTE_C4_X3: return (d->Ho / 4) * (d->Wo / 64);          // one chunk per 4 x 64 tile
+    case ROUTE_S2U: return s2u_stats_chunks(g);                                   // one chunk per workgroup (row segment x strip of input rows)
+    case ROUTE_S2F: case ROUTE_S2F_X3: return s2f_stats_chunks(g);                // one chunk per 256-pixel tile of the phase grid (all four phases summed)
+    case ROUTE_S2D: return s2d_stats_chunks(g);                                   // one chunk per workgroup (row segment x strip of output rows)
+    default: break;
     }
     static const bool no_x3_stats = DL_DEV_ENV("DL_NO_X3_STATS") != nullptr;       // A/B: strict policy with the stand-alone statistics pass
-    const int bm = (x3_glds_applies(d) && !no_x3_stats) ? x3_tile_bm(d) : glds_tile_bm(d);
-    const int hw = d->Hq * d->Wq;
-    if (bm == 0 || hw % bm) return 0;
+    if (no_x3_stats && route_is_x3_tile(r)) return 0;
+    const int bm = g_routes[r].bm, hw = d->Hq * d->Wq;
+    if (bm == 0 || hw % bm) return 0;          // (the PatchGAN kernels and conv_gemm_kernel have none; tiles must not straddle images)
     return (hw / bm) * d->n_phase;
 }
 
+// Fused statistics are offered where the PLAIN launch of the descriptor takes a kernel that has them (a caller that asks for them on a descriptor of the
+// PatchGAN kernels gets 0 and runs the stand-alone pass behind the plain launch).
+extern "C" int dl_conv_stats_chunks(const dl_conv_desc *d) {
+    if (!d || !stats_fusable(d)) return 0;
+    ConvArgs g = conv_geometry(d);
+    return route_stats_chunks(conv_route(d, g, false, false, false), d, g);
+}
+
 extern "C" int dl_conv_bnstats_chunks(const dl_conv_desc *d) {
-    // the reductions live in the LDS-transposed store epilogue of the direct-to-LDS kernels (tile_epilogue_lds): bf16, >= 64 output
-    // channels per tile, no split-K, tiles that do not straddle images
+    // the reductions live in the LDS-transposed store epilogue of the direct-to-LDS kernels (tile_epilogue_lds): >= 64 output channels per tile, no
+    // split-K, tiles that do not straddle images; none of the special kernels has them
     static const bool off = DL_DEV_ENV("DL_OLD_EPILOGUE") != nullptr;
     static const char *p32 = DL_DEV_ENV("DL_CONV_P32");
-    if (!d || off || (p32 && p32[0] == '1') || d->Co <= 16 || d->act != DL_ACT_NONE || c4_eligible(d) || s2f_applies(d) || s2fx3_applies(d) || s2d_applies(d) || s2u_applies(d)) return 0;
+    if (!d || off || (p32 && p32[0] == '1') || d->Co <= 16 || !stats_fusable(d)) return 0;
+    ConvArgs g = conv_geometry(d);
+    const ConvRoute r = conv_route(d, g, false, false, false);
+    if (route_is_special(r)) return 0;
     static const int min_bm = DL_DEV_ENV("DL_BNSTATS_MIN_BM") ? atoi(DL_DEV_ENV("DL_BNSTATS_MIN_BM")) : 0;       // A/B: 256 = only the 256 x 256-tile kernels
-    if (glds_tile_bm(d) < min_bm) return 0;
-    return dl_conv_stats_chunks(d);
+    if ((route_is_x3_tile(r) ? 0 : g_routes[r].bm) < min_bm) return 0;
+    return route_stats_chunks(r, d, g);
 }
 
 static int conv_forward_impl(const dl_conv_desc *d, const void *in, const void *w_hi, const void *w_lo, const float *bias,
@@ -1900,7 +1838,9 @@ extern "C" int dl_conv_forward(const dl_conv_desc *d, const void *in, const void
 // connection (networks.py:509-513: out = x + conv_block(x)).  `addend` may be `out` itself (every thread reads its 16 bytes before it writes them).
 extern "C" int dl_conv_add_supported(const dl_conv_desc *d) {
     // (zero padding only: the data gradient of a reflect / replicate layer is the pad-0 plan over the padded extent + a fold, nothing to add to in place)
-    return d && d->splitk == 1 && !d->raw_out && d->pad_mode == DL_PAD_ZERO && strcmp(dl_conv_kernel_name(d), "conv_gemm_w4_kernel") == 0;
+    if (!d || d->splitk != 1 || d->raw_out || d->pad_mode != DL_PAD_ZERO) return 0;
+    ConvArgs g = conv_geometry(d);
+    return conv_route(d, g, false, false, false) == ROUTE_W4;
 }
 
 extern "C" int dl_conv_forward_add(const dl_conv_desc *d, const void *in, const void *w_hi, const void *w_lo, const void *addend, int32_t addend_pstride,
@@ -1950,27 +1890,27 @@ static int conv_forward_impl(const dl_conv_desc *d, const void *in, const void *
     for (int p = 0; p < d->n_phase; ++p)
         if (d->phase_kbase[p] % 64) DL_FAIL("dl_conv_forward: phase_kbase must be a multiple of 64");
 
-    ConvArgs a;
-    memset(&a, 0, sizeof(a));
-    a.in = in; a.w_hi = (const bf16_t *)w_hi; a.w_lo = (const bf16_t *)w_lo; a.bias = bias; a.out = out; a.slab = slab;
-    fill_conv_geometry(a, d);
+    if (!((d->in_dtype == DL_BF16 && d->prec == DL_PREC_BF16) || (d->in_dtype == DL_F32 && (d->prec == DL_PREC_BF16 || d->prec == DL_PREC_BF16X3))))
+        DL_FAIL("dl_conv_forward: unsupported dtype/precision combination (%d, %d)", d->in_dtype, d->prec);
     if (d->in_split && !(d->in_dtype == DL_F32 && d->prec == DL_PREC_BF16X3 && d->in_act == DL_ACT_NONE && x3_glds_applies(d)))
         DL_FAIL("dl_conv_forward: in_split needs the strict policy (fp32 + BF16X3) on the direct-to-LDS kernels and no input activation");
+
+    // the geometry, the decision taken on it alone (conv_route), then the pointers and per-call facts of this launch
+    ConvArgs a = conv_geometry(d);
+    const ConvRoute route = conv_route(d, a, bn != nullptr, stats_part != nullptr, add != nullptr);
+    if (stats_part) {
+        a.stats_nchunks = route_stats_chunks(conv_route(d, a, false, false, false), d, a);          // (what dl_conv_stats_chunks told the caller)
+        if (a.stats_nchunks == 0) DL_FAIL("dl_conv_forward: fused statistics are not available for this descriptor (ask dl_conv_stats_chunks first)");
+        a.stats_part = stats_part;
+    }
+    a.in = in; a.w_hi = (const bf16_t *)w_hi; a.w_lo = (const bf16_t *)w_lo; a.bias = bias; a.out = out; a.slab = slab;
     static const bool epi_old = DL_DEV_ENV("DL_OLD_EPILOGUE") != nullptr;
     a.epi_old = epi_old ? 1 : 0;
-    a.Mtot = d->N * d->Hq * d->Wq;
     // A/B switch: "1" = channel-chunk-major K steps.  Measured on MI355X (r01): 4-7% faster in an isolated loop over one layer
     // (tools/ab_order.sh) but 3-12% SLOWER inside the training step (profiles/r01: 162.9 -> 168.7 us on the 256x256 tile),
     // so tap-major stays the default.
     static const char *korder_env = DL_DEV_ENV("DL_CONV_KORDER");
     a.k_order = (korder_env && korder_env[0] == '1') ? 1 : 0;
-    a.stats_part = nullptr;
-    a.stats_nchunks = 0;
-    if (stats_part) {
-        a.stats_nchunks = dl_conv_stats_chunks(d);
-        if (a.stats_nchunks == 0) DL_FAIL("dl_conv_forward: fused statistics are not available for this descriptor (ask dl_conv_stats_chunks first)");
-        a.stats_part = stats_part;
-    }
     a.add = (const bf16_t *)add;
     a.add_pstride = add_pstride;
     if (bn) {
@@ -1978,23 +1918,37 @@ static int conv_forward_impl(const dl_conv_desc *d, const void *in, const void *
         a.bn_mean = bn->mean; a.bn_rstd = bn->rstd; a.bn_scale = bn->scale; a.bn_shift = bn->shift;
     }
 
-    int rc;
-    static const bool no_glds = DL_DEV_ENV("DL_NO_GLDS") != nullptr;      // A/B switch for profiling the two staging paths
-    const ConvRoute route = conv_route(d, bn != nullptr, stats_part != nullptr, add != nullptr);
-    if (route == ROUTE_DOT_FWD || route == ROUTE_DOT_DGRAD) return launch_conv_dot(a, route == ROUTE_DOT_FWD, stream);
-    if (route == ROUTE_C4) rc = launch_conv_c4(a, d, stream);
-    else if (route == ROUTE_D1) rc = launch_conv_d1(a, stream);
-    else if (route == ROUTE_D1G) rc = launch_conv_d1g(a, stream);
-    else if (route == ROUTE_C4_X3) rc = launch_conv_c4_x3(a, d, stream);
-    else if (route == ROUTE_S2U) rc = launch_conv_s2u(a, stream);
-    else if (route == ROUTE_S2F) rc = launch_conv_s2f(a, stream);
-    else if (route == ROUTE_S2F_X3) rc = launch_conv_s2f_x3(a, stream);
-    else if (route == ROUTE_S2D) rc = launch_conv_s2d(a, stream);
-    else if (d->in_dtype == DL_BF16 && d->prec == DL_PREC_BF16 && d->in_act == DL_ACT_NONE && !no_glds) rc = dispatch_tile_glds(a, stream);
-    else if (d->in_dtype == DL_BF16 && d->prec == DL_PREC_BF16) rc = dispatch_tile<bf16_t, bf16_t, 1>(a, stream);
-    else if (d->in_dtype == DL_F32 && d->prec == DL_PREC_BF16X3) rc = x3_glds_applies(d) ? dispatch_tile_x3(a, stream) : dispatch_tile<float, float, 3>(a, stream);
-    else if (d->in_dtype == DL_F32 && d->prec == DL_PREC_BF16) rc = dispatch_tile<float, float, 1>(a, stream);
-    else DL_FAIL("dl_conv_forward: unsupported dtype/precision combination (%d, %d)", d->in_dtype, d->prec);
+    int rc = -1;
+    switch (route) {
+    case ROUTE_DOT_FWD: return launch_conv_dot(a, true, stream);           // (these two have no split-K partials to reduce)
+    case ROUTE_DOT_DGRAD: return launch_conv_dot(a, false, stream);
+    case ROUTE_C4: rc = launch_conv_c4(a, d, stream); break;
+    case ROUTE_D1: rc = launch_conv_d1(a, stream); break;
+    case ROUTE_D1G: rc = launch_conv_d1g(a, stream); break;
+    case ROUTE_C4_X3: rc = launch_conv_c4_x3(a, d, stream); break;
+    case ROUTE_S2U: rc = launch_conv_s2u(a, stream); break;
+    case ROUTE_S2F: rc = launch_conv_s2f(a, stream); break;
+    case ROUTE_S2F_X3: rc = launch_conv_s2f_x3(a, stream); break;
+    case ROUTE_S2D: rc = launch_conv_s2d(a, stream); break;
+    case ROUTE_W4: rc = launch_conv_w4(a, stream); break;
+    case ROUTE_8PH: rc = launch_conv_8ph_variant(a, stream); break;
+    case ROUTE_GLDS_256x16: rc = launch_conv_glds<256, 16, 32, 4, 1>(a, stream); break;
+    case ROUTE_GLDS_128x64: rc = launch_conv_glds<128, 64, 64, 2, 2>(a, stream); break;
+    case ROUTE_GLDS_128x128: rc = launch_conv_glds<128, 128, 64, 2, 2>(a, stream); break;
+    case ROUTE_GLDS_256x256: rc = launch_conv_glds_256_variant(a, stream); break;
+#ifdef DL_DEV_SWITCHES
+    case ROUTE_P32: rc = launch_conv_p32_variant(a, stream); break;
+#endif
+    case ROUTE_GATHER_BF16: rc = dispatch_tile<bf16_t, bf16_t, 1>(a, stream); break;
+    case ROUTE_GATHER_F32: rc = d->prec == DL_PREC_BF16X3 ? dispatch_tile<float, float, 3>(a, stream) : dispatch_tile<float, float, 1>(a, stream); break;
+    case ROUTE_W4X3: rc = launch_conv_w4x3(a, stream); break;
+    case ROUTE_8PH_X3: rc = launch_conv_8ph_x3_variant(a, stream); break;
+    case ROUTE_X3_256x16: rc = launch_conv_glds_x3_tile<256, 16, 4, 1>(a, stream); break;
+    case ROUTE_X3_256x32: rc = launch_conv_glds_x3_tile<256, 32, 4, 1>(a, stream); break;
+    case ROUTE_X3_128x64: rc = launch_conv_glds_x3_tile<128, 64, 2, 2>(a, stream); break;
+    case ROUTE_X3_128x128: rc = launch_conv_glds_x3_tile<128, 128, 2, 2>(a, stream); break;
+    case ROUTE_COUNT: break;
+    }
     if (rc) return rc;
 
     if (d->splitk > 1) {

@@ -776,12 +776,12 @@ static int launch_conv_glds_x3(const ConvArgs &a, hipStream_t stream) {
     return launch_conv_glds_x3_impl<BM, BN, WM, WN, false, IN_ACT>(a, stream);
 }
 
-template <int IN_ACT>
-static int dispatch_glds_x3_tiles(const ConvArgs &a, hipStream_t stream) {
-    if (a.Co <= 16) return launch_conv_glds_x3<256, 16, 4, 1, IN_ACT>(a, stream);
-    if (a.Co <= 32) return launch_conv_glds_x3<256, 32, 4, 1, IN_ACT>(a, stream);      // the head's (co, kw)-stacked rows (21 -> 32): half the MFMAs of the 64-wide tile
-    if (a.Co <= 64) return launch_conv_glds_x3<128, 64, 2, 2, IN_ACT>(a, stream);
-    return launch_conv_glds_x3<128, 128, 2, 2, IN_ACT>(a, stream);
+// one tile of conv_gemm_glds_x3_kernel, chosen by conv_route(): the instantiation for the layer's input activation
+template <int BM, int BN, int WM, int WN>
+static int launch_conv_glds_x3_tile(const ConvArgs &a, hipStream_t stream) {
+    if (a.in_act == DL_ACT_RELU) return launch_conv_glds_x3<BM, BN, WM, WN, DL_ACT_RELU>(a, stream);
+    if (a.in_act == DL_ACT_LRELU) return launch_conv_glds_x3<BM, BN, WM, WN, DL_ACT_LRELU>(a, stream);
+    return launch_conv_glds_x3<BM, BN, WM, WN, DL_ACT_NONE>(a, stream);
 }
 
 // which strict-policy descriptors take the direct-to-LDS kernels of this file (DL_NO_X3_GLDS=1: none -- the round-1 register-staged kernel, A/B)
@@ -797,20 +797,6 @@ static bool x3_big_tile(int in_act, int pad_mode, int Ci, int mtot, int Co, int 
     return !no_big && in_act == DL_ACT_NONE && pad_mode == DL_PAD_ZERO && Ci >= 32 && big_tile_fills_gpu(mtot, Co, n_phase, splitk);
 }
 
-// tile height (pixels) of the strict direct-to-LDS dispatch (for dl_conv_stats_chunks)
-static int x3_tile_bm(const dl_conv_desc *d) {
-    if (x3_big_tile(d->in_act, d->pad_mode, d->Ci, d->N * d->Hq * d->Wq, d->Co, d->n_phase, d->splitk)) return 256;
-    return d->Co <= 32 ? 256 : 128;
-}
-
-static const char *x3_kernel_name(const dl_conv_desc *d) {
-    if (x3_big_tile(d->in_act, d->pad_mode, d->Ci, d->N * d->Hq * d->Wq, d->Co, d->n_phase, d->splitk)) return "conv_gemm_8ph_x3_kernel";
-    if (d->Co <= 16) return "conv_gemm_glds_x3_kernel<256,16>";
-    if (d->Co <= 32) return "conv_gemm_glds_x3_kernel<256,32>";
-    if (d->Co <= 64) return "conv_gemm_glds_x3_kernel<128,64>";
-    return "conv_gemm_glds_x3_kernel<128,128>";
-}
-
 // conv_gemm_w4x3_kernel (conv_w4x3.hip), the one-wave-per-SIMD tile for the strict policy: OPT-IN (DL_CONV_W4X3=1).  Same-box A/B (r04,
 // profiles/r04/w4x3_ab.txt): isolated forward 390-395 us vs 398-402 us for the 8-phase strict kernel, data gradient 346-350 vs 348-354, inside the strict
 // step 345.6-347.1 vs 343.7-344.2 us per launch and 204.8 vs 203.8 ms per step -- a tie.  Unlike the bf16 pair (conv_w4.hip: -13 %), the strict 8-phase
@@ -821,29 +807,24 @@ static bool w4x3_enabled() {
     return e && e[0] == '1';
 }
 
-static int dispatch_tile_x3(const ConvArgs &a, hipStream_t stream) {
-    if (x3_big_tile(a.in_act, a.pad_mode, a.Ci, a.Mtot, a.Co, a.n_phase, a.splitk)) {
-        if (w4x3_enabled() && w4x3_eligible(a)) return launch_conv_w4x3(a, stream);
+// conv_gemm_8ph_x3_kernel, chosen by conv_route(): the product instantiation, or one of its timing variants in the dev build
+static int launch_conv_8ph_x3_variant(const ConvArgs &a, hipStream_t stream) {
 #ifdef DL_DEV_SWITCHES      // timing-only ablations (results WRONG by construction) and schedule variants: dev build only
-        static const char *abl = DL_DEV_ENV("DL_CONV_ABLATE");
-        if (abl && abl[0] == '1') return launch_conv_8ph_x3<DL_ACT_NONE, 1>(a, stream);
-        if (abl && abl[0] == '2') return launch_conv_8ph_x3<DL_ACT_NONE, 2>(a, stream);
-        if (abl && abl[0] == '3') return launch_conv_8ph_x3<DL_ACT_NONE, 3>(a, stream);
-        if (abl && abl[0] == '4') return launch_conv_8ph_x3<DL_ACT_NONE, 4>(a, stream);
-        if (a.in_split) return launch_conv_8ph_x3<DL_ACT_NONE, 0>(a, stream);      // (the timing variants below re-split their input)
-        static const char *var = DL_DEV_ENV("DL_X3_VAR");
-        if (var && var[0] == '1') return launch_conv_8ph_x3<DL_ACT_NONE, 0, 1>(a, stream);
-        if (var && var[0] == '2') return launch_conv_8ph_x3<DL_ACT_NONE, 0, 2>(a, stream);
-        if (var && var[0] == '3') return launch_conv_8ph_x3<DL_ACT_NONE, 0, 3>(a, stream);
-        if (var && var[0] == '4') return launch_conv_8ph_x3<DL_ACT_NONE, 0, 4>(a, stream);
-        if (var && var[0] == '5') return launch_conv_8ph_x3<DL_ACT_NONE, 0, 5>(a, stream);
-        if (var && var[0] == '8') return launch_conv_8ph_x3<DL_ACT_NONE, 0, 8>(a, stream);
+    static const char *abl = DL_DEV_ENV("DL_CONV_ABLATE");
+    if (abl && abl[0] == '1') return launch_conv_8ph_x3<DL_ACT_NONE, 1>(a, stream);
+    if (abl && abl[0] == '2') return launch_conv_8ph_x3<DL_ACT_NONE, 2>(a, stream);
+    if (abl && abl[0] == '3') return launch_conv_8ph_x3<DL_ACT_NONE, 3>(a, stream);
+    if (abl && abl[0] == '4') return launch_conv_8ph_x3<DL_ACT_NONE, 4>(a, stream);
+    if (a.in_split) return launch_conv_8ph_x3<DL_ACT_NONE, 0>(a, stream);      // (the timing variants below re-split their input)
+    static const char *var = DL_DEV_ENV("DL_X3_VAR");
+    if (var && var[0] == '1') return launch_conv_8ph_x3<DL_ACT_NONE, 0, 1>(a, stream);
+    if (var && var[0] == '2') return launch_conv_8ph_x3<DL_ACT_NONE, 0, 2>(a, stream);
+    if (var && var[0] == '3') return launch_conv_8ph_x3<DL_ACT_NONE, 0, 3>(a, stream);
+    if (var && var[0] == '4') return launch_conv_8ph_x3<DL_ACT_NONE, 0, 4>(a, stream);
+    if (var && var[0] == '5') return launch_conv_8ph_x3<DL_ACT_NONE, 0, 5>(a, stream);
+    if (var && var[0] == '8') return launch_conv_8ph_x3<DL_ACT_NONE, 0, 8>(a, stream);
 #endif
-        return launch_conv_8ph_x3<DL_ACT_NONE, 0>(a, stream);
-    }
-    if (a.in_act == DL_ACT_RELU) return dispatch_glds_x3_tiles<DL_ACT_RELU>(a, stream);
-    if (a.in_act == DL_ACT_LRELU) return dispatch_glds_x3_tiles<DL_ACT_LRELU>(a, stream);
-    return dispatch_glds_x3_tiles<DL_ACT_NONE>(a, stream);
+    return launch_conv_8ph_x3<DL_ACT_NONE, 0>(a, stream);
 }
 
 // ------------------------------------------------------------------------------------------------------------------

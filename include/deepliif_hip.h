@@ -153,7 +153,7 @@ int dl_conv_add_supported(const dl_conv_desc *d);
 int dl_conv_forward_add(const dl_conv_desc *d, const void *in, const void *w_hi, const void *w_lo, const void *addend, int32_t addend_pstride,
                         void *out, void *stream);
 /* Name of the kernel dl_conv_forward would launch for `d` (static string, matches the rocprofv3 kernel name up to template
- * arguments).  Diagnostic only: bench.py labels its roofline line with it. */
+ * arguments): the very decision the launch takes, for every kernel.  Diagnostic only: bench.py labels its roofline line with it. */
 const char *dl_conv_kernel_name(const dl_conv_desc *d);
 
 /* ------------------------------------------------------------------------------------------------------------

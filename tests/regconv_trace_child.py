@@ -1,7 +1,7 @@
 """Child process of tests/test_gpu_regconv_sweep.py::test_kernel_names_match_the_traced_launches -- not a test module.
 
 Run under `rocprofv3 --kernel-trace`: one small dl_conv_forward per route of the dispatch (the six weights-in-registers kernels with and without fused
-statistics, with and without a bias, one dl_conv_forward_add, a few fallbacks) and, for each, one line
+statistics, with and without a bias, one dl_conv_forward_add, a few fallbacks, then the kernels of the tile family) and, for each, one line
 
     ROUTE <label> <dl_conv_kernel_name of the descriptor that was launched>
 
@@ -66,12 +66,37 @@ ROUTES = [
 ADD_SPEC, ADD_SHAPE = ConvSpec('conv', 256, 256, 3, 1, 1, L.PAD_ZERO, 0), (4, 128, 128)          # the ResnetBlock shape: dl_conv_forward_add (conv_gemm_w4_kernel)
 
 
+def _block(pad_mode):
+    return ConvSpec('conv', 256, 256, 3, 1, 1, pad_mode, 0)
+
+
+# the tile family, one forward launch per kernel at the smallest shape that reaches it: label, layer, N x H x W, strict policy?, input activation, the kernel
+TILE_ROUTES = [
+    ('w4@224-tiles', _block(L.PAD_ZERO), (4, 112, 128), False, L.ACT_NONE, 'conv_gemm_w4_kernel'),           # exactly the 224 tiles of the big-tile rule
+    ('w4+replicate@8-tiles', _block(L.PAD_REPLICATE), (1, 16, 128), False, L.ACT_NONE, 'conv_gemm_w4_kernel'),
+    ('8ph', _block(L.PAD_ZERO), (1, 256, 256), False, L.ACT_NONE, 'conv_gemm_8ph_kernel'),                    # rows not 128 pixels wide
+    ('glds256+reflect', _block(L.PAD_REFLECT), (1, 256, 256), False, L.ACT_NONE, 'conv_gemm_glds_kernel<256,256,64>'),
+    ('gather+lrelu-input', ConvSpec('conv', 64, 128, 3, 2, 1), (1, 16, 16), False, L.ACT_LRELU, 'conv_gemm_kernel<bf16>'),
+    ('8ph_x3@224-tiles', _block(L.PAD_ZERO), (4, 112, 128), True, L.ACT_NONE, 'conv_gemm_8ph_x3_kernel'),
+    ('glds_x3@8-tiles', _block(L.PAD_ZERO), (1, 16, 128), True, L.ACT_NONE, 'conv_gemm_glds_x3_kernel<128,128>'),
+]
+
+
+def tile_descriptor(spec, shape, strict, in_act):
+    n, h, w = shape
+    oh, ow = spec.out_hw(h, w)
+    dtype, prec = (L.DL_F32, L.PREC_BF16X3) if strict else (L.DL_BF16, L.PREC_BF16)
+    return RC.fill_conv_desc(spec.forward_plan(), n, h, w, RC.cpad(spec.cin), oh, ow, RC.cpad(spec.cout), RC.cpad(spec.cout), oh, ow, dtype, prec, L.ACT_NONE,
+                             in_act, spec.cout, 1)
+
+
 C_ABI_ROUTES = [('d1g+bias-pointer-without-entries', D1G, (64, 6, 4, 4)), ('dot_dgrad+bias-pointer-without-entries', DOTG, (1, 512, 4, 4))]
 
 
 def route_cases():
     """label -> case of every route, in launch order (the parent derives the expected launch grids of the strip kernels from the cases)"""
-    return [(label, case) for label, case, _, _ in ROUTES] + [(label, case) for label, case, _ in C_ABI_ROUTES] + [('conv_forward_add', None)]
+    return [(label, case) for label, case, _, _ in ROUTES] + [(label, case) for label, case, _ in C_ABI_ROUTES] + [('conv_forward_add', None)] + \
+        [(row[0], None) for row in TILE_ROUTES]
 
 
 def workgroups(case):
@@ -100,6 +125,10 @@ def names_only():
     d = RC.fill_conv_desc(ADD_SPEC.dgrad_plan(), n, h, w, 256, h, w, 256, 256, h, w, L.DL_BF16, L.PREC_BF16, L.ACT_NONE, L.ACT_NONE, 0, 1)
     assert lib.dl_conv_add_supported(C.byref(d)) and RC.kernel_name(lib, d) == 'conv_gemm_w4_kernel'
     print(f'ROUTE conv_forward_add {RC.kernel_name(lib, d)}')
+    for label, spec, shape, strict, in_act, want in TILE_ROUTES:
+        name = RC.kernel_name(lib, tile_descriptor(spec, shape, strict, in_act))
+        print(f'ROUTE {label} {name}')
+        assert name == want, (label, name, want)
 
 
 def main():
@@ -148,6 +177,19 @@ def main():
     assert be.conv_forward_add(packed, x, addend, out, h, w_, L.PREC_BF16), 'dl_conv_forward_add is not available for the ResnetBlock shape'
     torch.cuda.synchronize()
     print(f'ROUTE conv_forward_add {be.last_conv_kernel}', flush=True)
+    for label, spec, (n, h, w_), strict, in_act, want in TILE_ROUTES:
+        plan = spec.forward_plan()
+        oh, ow = spec.out_hw(h, w_)
+        packed = ops.PackedWeights(plan, dev, strict)          # (the strict policy reads a lo weight plane)
+        be.pack_weights(packed, (torch.randn((spec.cout, spec.cin, spec.k, spec.k), generator=g) * 0.05).to(dev))
+        x = torch.randn((n, h, w_, RC.cpad(spec.cin)), generator=g).to(torch.float32 if strict else torch.bfloat16).to(dev)
+        out = torch.empty((n, oh, ow, RC.cpad(spec.cout)), dtype=x.dtype, device=dev)
+        bias = torch.randn(spec.cout, generator=g).to(dev)
+        be.conv_forward(packed, x, out, oh, ow, bias, L.ACT_NONE, in_act, L.PREC_BF16X3 if strict else L.PREC_BF16, splitk=1)
+        torch.cuda.synchronize()
+        name = be.last_conv_kernel
+        assert name == want, (label, name, want)
+        print(f'ROUTE {label} {name}', flush=True)
     print('CHILD DONE', flush=True)
 
 

@@ -276,10 +276,12 @@ _CONV_KERNEL = re.compile(r'conv_[a-z0-9_]*?kernel')
 
 @pytest.mark.skipif(DRY, reason='needs the profiler on a GPU')
 def test_kernel_names_match_the_traced_launches(tmp_path):
-    """dl_conv_kernel_name is a ladder of its own next to the launch ladder of dl_conv_forward; every 'the dispatch took the new kernel' assertion of the
-    suite reads the former.  A fresh child process (tests/regconv_trace_child.py) runs one small call per route under a kernel trace and prints the name the
-    library reports for each; the convolution kernels in the trace, in launch order, must be exactly those.  Where the reported name carries template arguments (the
-    tile of conv_gemm_glds_kernel) they must lead the traced kernel's; the launch grids of the strip kernels must be what conv_ref.strip_rows predicts."""
+    """dl_conv_kernel_name reports the decision of conv_route() (csrc/conv_gemm.hip), the same one the launch of dl_conv_forward switches on; every 'the
+    dispatch took the new kernel' assertion of the suite reads the name.  What only a trace can show is that each arm of the launch switch starts the kernel its
+    row of the name table says: a fresh child process (tests/regconv_trace_child.py) runs one small call per route -- the special kernels and the tile family --
+    under a kernel trace and prints the name the library reports for each; the convolution kernels in the trace, in launch order, must be exactly those.  Where
+    the reported name carries template arguments (the tile of conv_gemm_glds_kernel, the storage type of conv_gemm_kernel) they must lead the traced kernel's;
+    the launch grids of the strip kernels must be what conv_ref.strip_rows predicts."""
     prof = shutil.which('rocprofv3') or '/opt/rocm/bin/rocprofv3'
     assert os.path.exists(prof), 'rocprofv3 not found'
     cmd = ['timeout', '-k', '10', '300', prof, '--kernel-trace', '--output-format', 'csv', '-d', str(tmp_path), '--', sys.executable,
@@ -287,7 +289,7 @@ def test_kernel_names_match_the_traced_launches(tmp_path):
     r = subprocess.run(cmd, capture_output=True, text=True, cwd=ROOT)
     assert r.returncode == 0, f'exit {r.returncode}\n{r.stdout[-3000:]}\n{r.stderr[-3000:]}'
     routes = [ln.split(' ', 2)[1:] for ln in r.stdout.splitlines() if ln.startswith('ROUTE ')]
-    assert len(routes) >= 29 and 'CHILD DONE' in r.stdout, r.stdout[-3000:]
+    assert len(routes) >= 36 and 'CHILD DONE' in r.stdout, r.stdout[-3000:]
     import csv
     rows = []
     for dirpath, _, files in os.walk(tmp_path):
@@ -310,7 +312,8 @@ def test_kernel_names_match_the_traced_launches(tmp_path):
     for row, (label, name), (_, case) in zip(conv_rows, routes, cases):
         # template arguments the library reports (conv_gemm_glds_kernel<128,64,64>: the tile) are the leading template arguments of the traced kernel
         if '<' in name:
-            want_args = [a.strip() for a in name[name.index('<') + 1:name.rindex('>')].split(',')]
+            # (conv_gemm_kernel<bf16> / <f32>: the library names the storage type, the trace spells the C++ type of its first template argument)
+            want_args = [{'bf16': 'unsigned short', 'f32': 'float'}.get(a.strip(), a.strip()) for a in name[name.index('<') + 1:name.rindex('>')].split(',')]
             traced = row['Kernel_Name']
             got_args = [a.strip() for a in traced[traced.index('<') + 1:traced.rindex('>')].split(',')]
             assert got_args[:len(want_args)] == want_args, (label, name, traced)
