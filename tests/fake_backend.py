@@ -112,7 +112,15 @@ class FakeBackend:
 
     def conv_wgrad(self, P, Q, grad, k, step, pad, pad_mode, p_act, q_act, prec, accumulate, splitk=None, stack_kw=0, p_split=False, q_split=False):
         self._count('wgrad')
-        Pv, Qv = _act(p_act, P.float()), _act(q_act, Q.float())
+
+        def staged(t, act):
+            # raww_to_planes (csrc/wgrad.hip): the activation is applied in fp32 and the result rounded ONCE to the 16-bit format the MFMA multiplies; the strict
+            # policy (PREC_BF16X3) keeps the fp32 value (its hi / lo split is the kernels' arithmetic, not the formula's)
+            v = _act(act, t.float())
+            if act == L.ACT_NONE or prec != L.PREC_BF16:
+                return v
+            return v.to(t.dtype if t.dtype != torch.float32 else ops.H16_DTYPE[ops.half_format()]).float()
+        Pv, Qv = staged(P, p_act), staged(Q, q_act)
         CA, CB = grad.shape[0], grad.shape[1]
         N, Hp, Wp, _ = Pv.shape
         g = torch.zeros_like(grad)
