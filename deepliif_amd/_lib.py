@@ -155,6 +155,8 @@ SIGNATURES = {
     'dl_tile_resample_supported': (_i, [_i, _i]),
     'dl_tile_gather_resample_u8': (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _i, _i, C.c_uint32, _i, _vp, _vp, _i, _i, _vp, _i, _vp, _i, _i, _vp]),
     'dl_tile_paste_resample_u8': (_i, [_i, _vp, _i, _i, _i, _vp, _vp, _i, _i, _vp, _i, _vp, _i64, _vp]),
+    'dl_train_gather_supported': (_i, [_i, _i, _i, _i, _i, _i]),
+    'dl_train_gather_u8': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _i, _vp, _i, _i, _i, _vp, _i, _vp, _i, _i, _i, _vp]),
     'dl_probe_mfma16': (_i, [_vp, _vp, _vp, _vp]),
     'dl_probe_trread': (_i, [_vp, _vp, _vp]),
     'dl_probe_mfma_sustained_elems': (C.c_size_t, [_i]),

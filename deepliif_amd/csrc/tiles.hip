@@ -442,3 +442,231 @@ extern "C" int dl_tile_paste_resample_u8(int in_dtype, const void *tiles, int in
     }
     return 0;
 }
+
+// ---- training batches from 8-bit dataset rows (deepliif/data/aligned_dataset.py:36-113 AlignedDataset.__getitem__ after Image.open(...).convert('RGB'):
+// panel crop, then base_dataset.py:80-114 get_transform in PIL's order -- convert('L'), Image.resize, crop, FLIP_LEFT_RIGHT -- then ToTensor + Normalize as
+// lut[], then engine.to_engine).  Same integer resize as above, but one table PER AXIS (panel w2 x h -> new_w x new_h; a null table = PIL skips that pass),
+// a per-sample crop window and flip read from the device, and an LDS image that only holds the crop window's columns.
+#define DL_TRAIN_CHUNK 16         // samples per launch: their row pointers travel as kernel arguments
+
+struct TrainSrc {
+    const uint8_t *row[DL_TRAIN_CHUNK];
+    long long row_stride[DL_TRAIN_CHUNK];
+};
+
+__device__ __forceinline__ void train_src_of(const TrainSrc &src, int s, const uint8_t *&img, long long &row_stride) {
+    img = src.row[0];
+    row_stride = src.row_stride[0];
+#pragma unroll
+    for (int q = 1; q < DL_TRAIN_CHUNK; ++q)
+        if (q == s) { img = src.row[q]; row_stride = src.row_stride[q]; }
+}
+
+// the r | g << 8 | b << 16 word of panel pixel (y, x); gray: PIL's convert('L') in all three bytes
+__device__ __forceinline__ uint32_t train_pixel(const uint8_t *img, long long row_stride, int x_off, int y, int x, int gray) {
+    const uint8_t *p = img + (long long)y * row_stride + 3ll * (x_off + x);
+    const uint32_t r = p[0], g = p[1], b = p[2];
+    if (gray) {
+        const uint32_t l = (19595u * r + 38470u * g + 7471u * b + 0x8000u) >> 16;
+        return l | (l << 8) | (l << 16);
+    }
+    return r | (g << 8) | (b << 16);
+}
+
+// the per-sample record {crop_x, crop_y, flip}, clamped so that a wrong record cannot turn into an out-of-range read
+__device__ __forceinline__ void train_params(const int32_t *params, int s, int new_w, int new_h, int cw, int ch, int &cx, int &cy, int &flip) {
+    cx = params[3 * s];
+    cy = params[3 * s + 1];
+    flip = params[3 * s + 2] != 0;
+    cx = cx < 0 ? 0 : (cx > new_w - cw ? new_w - cw : cx);
+    cy = cy < 0 ? 0 : (cy > new_h - ch ? new_h - ch : cy);
+}
+
+// channels [c0, c0 + nch) of one output pixel <- lut[] of the word's bytes, channels up to zero_to <- 0 (as nchw_to_nhwc_kernel); one 8-channel vector
+// store when the call owns the whole group
+template <typename T>
+__device__ __forceinline__ void train_store(T *o, uint32_t word, const float *__restrict__ lut, int c0, int nch, int zero_to) {
+    if ((c0 & 7) == 0 && zero_to == c0 + 8) {
+        float v[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) v[j] = 0.f;
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+            if (k < nch) v[k] = lut[(word >> (8 * k)) & 0xff];
+        Vec8<T>::store(o + c0, v);
+        return;
+    }
+    for (int k = 0; k < nch; ++k) store1<T>(o + c0 + k, lut[(word >> (8 * k)) & 0xff]);
+    for (int c = c0 + nch; c < zero_to; ++c) store1<T>(o + c, 0.f);
+}
+
+// no resize on either axis: crop + flip + lut, one thread per output pixel, no LDS
+template <typename T>
+__global__ void __launch_bounds__(256) train_gather_kernel(TrainSrc src, int x_off, int w2, int h, int gray, const int32_t *__restrict__ params, int ch, int cw,
+                                                           const float *__restrict__ lut, T *__restrict__ out, int out_pstride, int c0, int nch, int zero_to) {
+    const int s = blockIdx.y;
+    const int pix = blockIdx.x * blockDim.x + threadIdx.x;
+    if (pix >= ch * cw) return;
+    const int oy = pix / cw, ox = pix - oy * cw;
+    int cx, cy, flip;
+    train_params(params, s, w2, h, cw, ch, cx, cy, flip);
+    const uint8_t *img;
+    long long row_stride;
+    train_src_of(src, s, img, row_stride);
+    const uint32_t word = train_pixel(img, row_stride, x_off, cy + oy, cx + (flip ? cw - 1 - ox : ox), gray);
+    train_store<T>(out + ((long long)s * ch * cw + pix) * out_pstride, word, lut, c0, nch, zero_to);
+}
+
+// One workgroup = one sample and a strip of R rows of its crop window.  mid[rows_cap][cw]: the panel rows the strip's vertical taps reach (tby.bounds of
+// the first and the last row; without a vertical table the strip's own rows), horizontally resized, columns crop_x .. crop_x + cw - 1 only.
+template <typename T>
+__global__ void __launch_bounds__(256) train_gather_resample_kernel(TrainSrc src, int x_off, int w2, int h, int gray, int new_w, RsTable tbx, int new_h, RsTable tby,
+                                                                    const int32_t *__restrict__ params, int ch, int cw, int R, int rows_cap,
+                                                                    const float *__restrict__ lut, T *__restrict__ out, int out_pstride, int c0, int nch,
+                                                                    int zero_to) {
+    extern __shared__ uint32_t rs_lds[];
+    uint32_t *mid = rs_lds;
+    const int s = blockIdx.y;
+    const int y0 = blockIdx.x * R, y1 = y0 + R < ch ? y0 + R : ch;          // rows of the crop window
+    if (y0 >= y1) return;
+    int cx, cy, flip;
+    train_params(params, s, new_w, new_h, cw, ch, cx, cy, flip);
+    const uint8_t *img;
+    long long row_stride;
+    train_src_of(src, s, img, row_stride);
+    int ya = cy + y0, rows = y1 - y0;
+    if (tby.bounds) {
+        int na, yb, nb;
+        rs_taps(tby, cy + y0, h, ya, na);
+        rs_taps(tby, cy + y1 - 1, h, yb, nb);
+        rows = yb + nb - ya;
+    }
+    rows = rows < 0 ? 0 : (rows > rows_cap ? rows_cap : rows);
+    for (int i = threadIdx.x; i < rows * cw; i += blockDim.x) {
+        const int row = i / cw, xx = cx + (i - row * cw);
+        if (!tbx.bounds) {
+            mid[i] = train_pixel(img, row_stride, x_off, ya + row, xx, gray);
+            continue;
+        }
+        int x0, n;
+        rs_taps(tbx, xx, w2, x0, n);
+        const int32_t *k = tbx.kk + (long long)xx * tbx.ksize;
+        int a0 = 1 << (DL_RS_BITS - 1), a1 = a0, a2 = a0;
+        for (int j = 0; j < n; ++j) {
+            const uint32_t m = train_pixel(img, row_stride, x_off, ya + row, x0 + j, gray);
+            const int kj = k[j];
+            a0 += (int)(m & 0xff) * kj;
+            a1 += (int)((m >> 8) & 0xff) * kj;
+            a2 += (int)((m >> 16) & 0xff) * kj;
+        }
+        mid[i] = rs_pack(a0, a1, a2);
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < (y1 - y0) * cw; i += blockDim.x) {
+        const int ry = i / cw, ox = i - ry * cw;
+        const int col = flip ? cw - 1 - ox : ox;
+        uint32_t word = 0;
+        if (tby.bounds) word = rs_vertical(tby, mid, cw, ya, rows, cy + y0 + ry, col, h);
+        else if (ry < rows) word = mid[ry * cw + col];
+        train_store<T>(out + (((long long)s * ch + (y0 + ry)) * cw + ox) * out_pstride, word, lut, c0, nch, zero_to);
+    }
+}
+
+// strip height of the crop window and the LDS image it needs: rows_cap source rows of cw words
+static int train_rows_cap(int h, int new_h, int resize_y, int R) { return resize_y ? rs_rows_cap(h, new_h, R) : R; }
+static size_t train_lds_bytes(int h, int new_h, int resize_y, int cw, int R) { return 4ull * cw * (size_t)train_rows_cap(h, new_h, resize_y, R); }
+static int train_strip_rows(int h, int new_h, int resize_y, int ch, int cw) {
+    for (int R = ch < DL_RS_MAX_STRIP ? ch : DL_RS_MAX_STRIP; R >= 1; --R)
+        if (train_lds_bytes(h, new_h, resize_y, cw, R) <= DL_RS_LDS_BYTES) return R;
+    return 0;
+}
+// the checks on the geometry that dl_train_gather_u8 and dl_train_gather_supported share; panels = panel index + 1
+static int train_geometry_ok(const char *who, int w2, int h, int panels, int new_w, int new_h, int ch, int cw) {
+    if (w2 <= 0 || h <= 0 || new_w <= 0 || new_h <= 0 || ch <= 0 || cw <= 0 || panels <= 0)
+        DL_FAIL("%s: empty problem (panel %dx%d -> %dx%d, crop %dx%d, panel index %d)", who, w2, h, new_w, new_h, cw, ch, panels - 1);
+    if (cw > new_w || ch > new_h) DL_FAIL("%s: the crop window %dx%d does not fit the resized panel %dx%d", who, cw, ch, new_w, new_h);
+    if (3ll * panels * w2 > 0x7fffffffll || (long long)ch * cw > 0x7fffffffll || (long long)new_w * rs_ksize(w2, new_w) > 0x7fffffffll ||
+        (long long)new_h * rs_ksize(h, new_h) > 0x7fffffffll)
+        DL_FAIL("%s: panel %dx%d (index %d) -> %dx%d, crop %dx%d overflows the kernel's 32-bit offsets", who, w2, h, panels - 1, new_w, new_h, cw, ch);
+    return 0;
+}
+
+extern "C" int dl_train_gather_supported(int w2, int h, int new_w, int new_h, int ch, int cw) {
+    if (train_geometry_ok("dl_train_gather_supported", w2, h, 1, new_w, new_h, ch, cw)) return 0;
+    if (new_w == w2 && new_h == h) return ch < DL_RS_MAX_STRIP ? ch : DL_RS_MAX_STRIP;          // plain kernel, no LDS: any strip height is accepted
+    const int R = train_strip_rows(h, new_h, new_h != h, ch, cw);
+    if (R < 1)
+        dl_set_error("dl_train_gather_supported: %d -> %d rows at a crop width of %d needs %zu bytes of LDS for one output row, the limit is %d", h, new_h, cw,
+                     train_lds_bytes(h, new_h, new_h != h, cw, 1), DL_RS_LDS_BYTES);
+    return R < 1 ? 0 : R;
+}
+
+extern "C" int dl_train_gather_u8(const void *const *rows, const int64_t *row_strides, int n, int w2, int h, int panel, int gray, int new_w, const int32_t *xbounds,
+                                  const int32_t *xkk, int xksize, int new_h, const int32_t *ybounds, const int32_t *ykk, int yksize, const int32_t *params, int ch,
+                                  int cw, int strip_rows, const float *lut, int out_dtype, void *out, int out_pstride, int out_c0, int zero_pad_to, void *stream) {
+    if (n <= 0) DL_FAIL("dl_train_gather_u8: empty problem (n=%d)", n);
+    if (panel < 0) DL_FAIL("dl_train_gather_u8: panel index %d", panel);
+    if (train_geometry_ok("dl_train_gather_u8", w2, h, panel + 1, new_w, new_h, ch, cw)) return -1;
+    if (!rows || !row_strides || !params || !lut || !out) DL_FAIL("dl_train_gather_u8: rows, row_strides, params, lut and out are required");
+    if (out_dtype != DL_F32 && out_dtype != DL_BF16) DL_FAIL("dl_train_gather_u8: dtype %d", out_dtype);
+    const int nch = gray ? 1 : 3;
+    if (out_c0 < 0 || out_c0 + nch > out_pstride || (zero_pad_to > out_c0 + nch && zero_pad_to > out_pstride))
+        DL_FAIL("dl_train_gather_u8: bad channel geometry (%d channels at %d, zero to %d, pstride=%d)", nch, out_c0, zero_pad_to, out_pstride);
+    if (out_pstride % 8) DL_FAIL("dl_train_gather_u8: engine tensors have a multiple of 8 padded channels (pstride=%d)", out_pstride);
+    if ((long long)n * ch * cw * out_pstride > 0x7fffffffffffll) DL_FAIL("dl_train_gather_u8: output of %d x %d x %d x %d elements is too large", n, ch, cw, out_pstride);
+    for (int i = 0; i < n; ++i)
+        if (!rows[i] || row_strides[i] < 3ll * (panel + 1) * w2) DL_FAIL("dl_train_gather_u8: sample %d: null row or a row stride (%lld) shorter than %d panels of %d pixels",
+                                                                         i, (long long)row_strides[i], panel + 1, w2);
+    const int resize_x = new_w != w2, resize_y = new_h != h;
+    if (resize_x != (xbounds != nullptr) || resize_x != (xkk != nullptr))
+        DL_FAIL("dl_train_gather_u8: width %d -> %d %s (PIL skips a pass that does not change the size)", w2, new_w, resize_x ? "needs a table" : "takes no table");
+    if (resize_y != (ybounds != nullptr) || resize_y != (ykk != nullptr))
+        DL_FAIL("dl_train_gather_u8: height %d -> %d %s (PIL skips a pass that does not change the size)", h, new_h, resize_y ? "needs a table" : "takes no table");
+    if (resize_x && xksize != rs_ksize(w2, new_w)) DL_FAIL("dl_train_gather_u8: xksize=%d, the table of %d -> %d has %d", xksize, w2, new_w, rs_ksize(w2, new_w));
+    if (resize_y && yksize != rs_ksize(h, new_h)) DL_FAIL("dl_train_gather_u8: yksize=%d, the table of %d -> %d has %d", yksize, h, new_h, rs_ksize(h, new_h));
+    if (strip_rows < 0) DL_FAIL("dl_train_gather_u8: strip_rows=%d", strip_rows);
+    int R = 0, rows_cap = 0;
+    size_t lds = 0;
+    if (resize_x || resize_y) {
+        if (strip_rows > ch) DL_FAIL("dl_train_gather_u8: strips of %d rows in a crop window of %d rows", strip_rows, ch);
+        R = strip_rows > 0 ? strip_rows : train_strip_rows(h, new_h, resize_y, ch, cw);
+        // the library's choice: shorter strips while the batch gives fewer than two workgroups per CU (each halving repeats at most ksize source rows per strip)
+        while (strip_rows == 0 && R > 8 && (long long)n * ((ch + R - 1) / R) < 512) R = (R + 1) / 2;
+        if (R < 1 || train_lds_bytes(h, new_h, resize_y, cw, R) > DL_RS_LDS_BYTES)
+            DL_FAIL("dl_train_gather_u8: %d -> %d rows at a crop width of %d with strips of %d rows needs %zu bytes of LDS, the limit is %d", h, new_h, cw, R < 1 ? 1 : R,
+                    train_lds_bytes(h, new_h, resize_y, cw, R < 1 ? 1 : R), DL_RS_LDS_BYTES);
+        rows_cap = train_rows_cap(h, new_h, resize_y, R);
+        lds = train_lds_bytes(h, new_h, resize_y, cw, R);
+    }
+    const RsTable tbx = {xbounds, xkk, xksize}, tby = {ybounds, ykk, yksize};
+    const int zero_to = zero_pad_to > out_c0 + nch ? zero_pad_to : out_c0 + nch;
+    for (int s0 = 0; s0 < n; s0 += DL_TRAIN_CHUNK) {
+        const int ns = n - s0 < DL_TRAIN_CHUNK ? n - s0 : DL_TRAIN_CHUNK;
+        TrainSrc src;
+        for (int i = 0; i < DL_TRAIN_CHUNK; ++i) {
+            src.row[i] = (const uint8_t *)rows[s0 + (i < ns ? i : 0)];
+            src.row_stride[i] = row_strides[s0 + (i < ns ? i : 0)];
+        }
+        const size_t o0 = (size_t)s0 * ch * cw * out_pstride;
+        const int32_t *pr = params + 3 * (size_t)s0;
+        if (!resize_x && !resize_y) {
+            dim3 grid((unsigned)(((long long)ch * cw + 255) / 256), ns);
+            if (out_dtype == DL_BF16)
+                hipLaunchKernelGGL(train_gather_kernel<bf16_t>, grid, dim3(256), 0, (hipStream_t)stream, src, panel * w2, w2, h, gray, pr, ch, cw, lut, (bf16_t *)out + o0,
+                                   out_pstride, out_c0, nch, zero_to);
+            else
+                hipLaunchKernelGGL(train_gather_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, src, panel * w2, w2, h, gray, pr, ch, cw, lut, (float *)out + o0,
+                                   out_pstride, out_c0, nch, zero_to);
+        } else {
+            dim3 grid((ch + R - 1) / R, ns);
+            if (out_dtype == DL_BF16)
+                hipLaunchKernelGGL(train_gather_resample_kernel<bf16_t>, grid, dim3(256), lds, (hipStream_t)stream, src, panel * w2, w2, h, gray, new_w, tbx, new_h, tby, pr,
+                                   ch, cw, R, rows_cap, lut, (bf16_t *)out + o0, out_pstride, out_c0, nch, zero_to);
+            else
+                hipLaunchKernelGGL(train_gather_resample_kernel<float>, grid, dim3(256), lds, (hipStream_t)stream, src, panel * w2, w2, h, gray, new_w, tbx, new_h, tby, pr,
+                                   ch, cw, R, rows_cap, lut, (float *)out + o0, out_pstride, out_c0, nch, zero_to);
+        }
+        DL_CHECK_LAUNCH("dl_train_gather_u8");
+    }
+    return 0;
+}

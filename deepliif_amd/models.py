@@ -42,6 +42,14 @@ def _get(opt, name, default):
     return getattr(opt, name) if hasattr(opt, name) else default
 
 
+def _adopt_act(a, prec, device):
+    """an activation handed to set_input (deepliif_amd.data): used as it is, so it must already be what to_engine would have made"""
+    if not isinstance(a, E.Act) or a.t.dtype != prec.dtype or a.t.device != device:
+        raise TypeError(f'set_input: an engine.Act batch must be {prec.dtype} on {device} (the loader takes precision and device from the same opt); '
+                        f'got {type(a).__name__}' + (f' {a.t.dtype} on {a.t.device}' if isinstance(a, E.Act) else ''))
+    return a.detach()
+
+
 def init_input_and_mod_id(opt, dir_model=None):
     """deepliif/util/util.py:242-270 for a fresh training run / explicit opt fields (file-name sniffing of existing
     checkpoints is done by the reference's Options object, which passes mod_id_seg / input_id through opt)."""
@@ -114,7 +122,9 @@ class StepGraph:
     captures, every later one replays.  Results are bit-identical to the eager step (tests/test_gpu_graph.py: reference trajectories).
     Falls back to eager for good, saying why, when the step cannot be captured: data-parallel exchange active (collectives are launched from tape
     callbacks on RCCL's own streams), dropout in training mode unless capture_dropout is set (the mask seed is a kernel argument), an optimizer
-    other than FusedAdam, a model class with host-side randomness (CycleGAN's ImagePool)."""
+    other than FusedAdam, a model class with host-side randomness (CycleGAN's ImagePool).
+    The batch is a dict of NCHW tensors: the engine.Act batches of deepliif_amd.data.create_dataset are out of scope here (a captured region replays
+    fixed addresses, the loader hands out fresh activations)."""
 
     def __init__(self, model, warmup: int = 2, capture_dropout: bool = False):
         self.model, self.warmup = model, max(2, warmup)      # two eager steps: the second one still creates state (the repack table sees the data-gradient images)
@@ -695,7 +705,26 @@ class DeepLIIFModel(BaseModel):
 
     # ---------------------------------------------------------------------------------------------------------
     def set_input(self, input):
-        """DeepLIIF_model.py:153-173: dict{'A': Tensor|list, 'B': list[Tensor], 'A_paths'}; tensors NCHW fp32 in [-1, 1]."""
+        """DeepLIIF_model.py:153-173: dict{'A': Tensor|list, 'B': list[Tensor], 'A_paths'}; tensors NCHW fp32 in [-1, 1].
+
+        A batch of deepliif_amd.data.create_dataset carries engine.Act values instead: they become _A / _B[i] / _Bseg as they are (no
+        to_engine, no layout pass), and real_A / real_B_* are E.from_engine of them -- under a 16-bit policy these are the values the
+        networks see (the tensors rounded to the policy's type), not the fp32 values the reference would show."""
+        if isinstance(input['A'], E.Act):
+            M, S = self.opt.modalities_no, self.mod_id_seg
+            self._A = _adopt_act(input['A'], self.precision, self.device)
+            acts = [_adopt_act(b, self.precision, self.device) for b in input['B']]
+            self._B = acts[:M]
+            self._Bseg = acts[M] if self.seg_gen else None
+            self.real_A = E.from_engine(self._A)
+            self.real_B_array = [E.from_engine(b) for b in acts]
+            for i in range(M):
+                setattr(self, f'real_B_{i + 1}', self.real_B_array[i])
+            if self.seg_gen:
+                setattr(self, f'real_B_{S}', self.real_B_array[M])
+            self.image_paths = input.get('A_paths', [])
+            self._real_pairs = None
+            return
         A = input['A']
         if isinstance(A, list):
             A = torch.cat([a.to(self.device) for a in A], dim=1)
@@ -911,8 +940,22 @@ class DeepLIIFExtModel(BaseModel):
 
     def set_input(self, input):
         """DeepLIIFExt_model.py:134-158: dict{'A', 'B': list, 'BS': list, 'A_paths'}  (SDG: 'A' is a list of input modalities,
-        concatenated on the channel axis, SDG_model.py:108-110)."""
+        concatenated on the channel axis, SDG_model.py:108-110).
+
+        A batch of deepliif_amd.data.create_dataset carries engine.Act values instead (SDG: ONE Act with the input modalities in its channel
+        slices): they become _A / _B[i] / _BS[i] as they are, and real_A / real_B / real_BS are E.from_engine of them -- under a 16-bit
+        policy the values the networks see, not the reference's fp32 values."""
         p = self.precision
+        if isinstance(input['A'], E.Act):
+            self._A = _adopt_act(input['A'], p, self.device)
+            self._B = [_adopt_act(b, p, self.device) for b in input['B']]
+            self._BS = [_adopt_act(b, p, self.device) for b in input.get('BS', [])]
+            self.real_A = E.from_engine(self._A)
+            self.real_B = [E.from_engine(b) for b in self._B]
+            self.real_BS = [E.from_engine(b) for b in self._BS]
+            self.image_paths = input.get('A_paths', [])
+            self._real_cat = None
+            return
         A = input['A']
         self.real_A = torch.cat([a.to(self.device) for a in A], dim=1) if isinstance(A, (list, tuple)) else A.to(self.device)
         self.real_B = [b.to(self.device) for b in input['B']]
@@ -1161,8 +1204,9 @@ class CycleGANModel(BaseModel):
     the GENERATOR update first -- loss_G = sum_i w_i [GAN(DA_i(fake_B_i)) + VGG(fake_B_i, B_i) + GAN(DB_i(fake_A_i)) + VGG(fake_A_i, A)]
     + 10/M sum_i [L1(rec_A_i, A) + L1(rec_B_i, B_i)], identity terms off (:207-208, 213) -- then the discriminators on the pooled, detached fakes,
     one backward per discriminator of (real + fake) * 0.5 * w_i (:172-205).  Every generator runs TWICE on the generator tape.
-    The VGG term carries no lambda here (:232, 238): it needs the weight file like everywhere else (BaseModel._make_vgg rules)."""
-    graphable = False          # may StepGraph capture optimize_parameters()? (no host-side randomness / per-step host state)
+    The VGG term carries no lambda here (:232, 238): it needs the weight file like everywhere else (BaseModel._make_vgg rules).
+    set_input takes NCHW tensors only: its data is unaligned, which deepliif_amd.data.create_dataset (aligned rows -> engine.Act batches) does not cover."""
+    graphable = False         # may StepGraph capture optimize_parameters()? (no host-side randomness / per-step host state)
 
     LAMBDA_A = LAMBDA_B = 10.0
 

@@ -907,6 +907,42 @@ class HipBackend:
         self.check(self.lib.dl_tile_paste_resample_u8(dt, tp, ps, net, tile, _ptr(bounds), _ptr(kk), kk.shape[1], strip_rows, _ptr(rects), rects.shape[0], _ptr(dst),
                                                    dst.stride(0), _stream(dst)), 'dl_tile_paste_resample_u8')
 
+    # ---- training batches from 8-bit dataset rows (deepliif_amd/data.py): panel crop, convert('L'), PIL's resize with one table per axis, per-sample crop
+    # and flip, lut, engine layout.  rows: uint8 [h, >= (panel + 1) * w2, 3] device tensors, one per sample; new_size = (new_w, new_h); tables = (x, y), each
+    # None (that axis keeps its size) or (bounds, kk) of tiling.resample_table; params: int32 [n, 3] = (crop_x, crop_y, flip) on the device
+    def train_gather_supported(self, w2, h, new_w, new_h, ch, cw) -> int:
+        """the strip height the library would choose, 0 when dl_train_gather_u8 refuses the geometry (self.train_gather_limit() then says why)"""
+        return int(self.lib.dl_train_gather_supported(int(w2), int(h), int(new_w), int(new_h), int(ch), int(cw)))
+
+    def train_gather_limit(self) -> str:
+        return self.lib.dl_last_error().decode('utf-8', 'replace')
+
+    def train_gather(self, rows, w2, h, panel, gray, new_size, tables, params, lut, out, c0, zero_pad_to, strip_rows=0):
+        new_w, new_h = new_size
+        flat = [t for tb in tables if tb is not None for t in tb]
+        _need_cuda(params, lut, out, *flat, *rows)
+        n = len(rows)
+        assert n >= 1 and params.dtype == torch.int32 and params.is_contiguous() and tuple(params.shape) == (n, 3)
+        assert lut.dtype == torch.float32 and lut.numel() == 256 and lut.is_contiguous()
+        assert out.dim() == 4 and out.shape[0] == n
+        for r in rows:
+            assert r.dtype == torch.uint8 and r.dim() == 3 and r.shape[2] == 3 and r.stride(2) == 1 and r.stride(1) == 3, 'dataset rows are uint8 [h, w, 3], pixels packed'
+            assert r.shape[0] == h and r.shape[1] >= (panel + 1) * w2, (tuple(r.shape), h, w2, panel)
+        args = []
+        for tb, new in zip(tables, (new_w, new_h)):
+            if tb is None:
+                args += [None, None, 0]
+                continue
+            bounds, kk = tb
+            assert bounds.dtype == torch.int32 and kk.dtype == torch.int32 and bounds.is_contiguous() and kk.is_contiguous()
+            assert tuple(bounds.shape) == (new, 2) and kk.shape[0] == new
+            args += [_ptr(bounds), _ptr(kk), kk.shape[1]]
+        ptrs = (C.c_void_p * n)(*[r.data_ptr() for r in rows])
+        strides = (C.c_int64 * n)(*[r.stride(0) for r in rows])
+        self.check(self.lib.dl_train_gather_u8(ptrs, strides, n, w2, h, panel, 1 if gray else 0, new_w, *args[:3], new_h, *args[3:], _ptr(params), out.shape[1],
+                                            out.shape[2], strip_rows, _ptr(lut), dl_dtype(out), _ptr(out), pstride(out), c0, zero_pad_to, _stream(out)),
+                   'dl_train_gather_u8')
+
     # ---- losses
     def loss(self, kind, x, target, target_const, C_real, loss_out, grad, grad_scale, out_scale=1.0, accumulate=False):
         """loss_out[0] = (accumulate ? loss_out[0] : 0) + out_scale * mean loss; grad = grad_scale * d(mean loss)/dx"""

@@ -533,6 +533,35 @@ int dl_tile_gather_resample_u8(const void *const *imgs /*host array of device po
 int dl_tile_paste_resample_u8(int in_dtype, const void *tiles, int in_pstride, int net, int tile, const int32_t *bounds, const int32_t *kk, int ksize,
                               int strip_rows, const int32_t *rects, int n_rects, void *dst, int64_t dst_row_stride, void *stream);
 
+/* Training batches from 8-bit dataset rows: everything AlignedDataset.__getitem__ (deepliif/data/aligned_dataset.py:36-113) does after
+ * Image.open(...).convert('RGB'), for one panel of every sample of a batch, fused with engine.to_engine.  A dataset row is one wide
+ * uint8 RGB image [h][num_img * w2][3] in HBM; panel i is its columns w2 * i .. w2 * (i + 1) - 1 (:62-63, :74).  Per output pixel, in
+ * PIL's order (base_dataset.py:80-114 get_transform with explicit params):
+ *     1. gray != 0: convert('L'), L = (19595 R + 38470 G + 7471 B + 0x8000) >> 16 (transforms.Grayscale(1), :83-84) -> 1 channel
+ *     2. Image.resize w2 x h -> new_w x new_h (:85-89, :97-98) with ONE TABLE PER AXIS, each as described for the resampled tiles
+ *        above ({x,y}bounds [new][2], {x,y}kk [new][ksize]); horizontal pass first, rounded to uint8, vertical pass over those bytes.
+ *        A NULL table means that axis keeps its size (new == old is then required, and a table is refused): Pillow skips that pass,
+ *        and with both NULL the resize is a plain copy
+ *     3. crop rows crop_y .. crop_y + ch - 1, columns crop_x .. crop_x + cw - 1 of the resized panel (__crop :137-143)
+ *     4. flip != 0: FLIP_LEFT_RIGHT, output column ox reads cropped column cw - 1 - ox (__flip :146-149)
+ *     5. lut[byte] (ToTensor + Normalize, 256 floats from the caller), rounded to the output type as dl_nchw_to_nhwc rounds
+ * params: device int32 [n][3] = {crop_x, crop_y, flip} per sample (clamped into the resized panel by the kernels).  out: engine tensor
+ * [n][ch][cw][out_pstride]; the call writes channels out_c0 .. out_c0 + (gray ? 1 : 3) - 1 and zeroes the channels from there up to
+ * zero_pad_to (as dl_nchw_to_nhwc; several input panels go to channel slices of one tensor, one call each).  rows / row_strides:
+ * host arrays of n device pointers and strides in bytes.  With a resize one workgroup owns one sample and a strip of R rows of the
+ * crop window; the horizontally resized panel rows its vertical taps reach live in LDS, the crop window's columns only (4 * cw bytes
+ * per row, 64 KB in all), never in HBM.  strip_rows = 0 lets the library choose R (at most 32, shortened while the batch leaves CUs
+ * idle); a positive value is used as given and fails if it does not fit or exceeds ch.  Without a resize: one thread per pixel, no LDS.
+ *   dl_train_gather_supported   the largest R the library would use for this geometry; 0 (and a dl_last_error() that names the
+ *                               limit) exactly where dl_train_gather_u8 with strip_rows = 0 and panel 0 would fail on the geometry:
+ *                               an empty problem, a crop window larger than the resized panel, 32-bit offsets, or an LDS image
+ *                               that does not fit with R = 1. */
+int dl_train_gather_supported(int w2, int h, int new_w, int new_h, int ch, int cw);
+int dl_train_gather_u8(const void *const *rows /*host array of device pointers*/, const int64_t *row_strides /*host*/, int n, int w2, int h, int panel,
+                       int gray, int new_w, const int32_t *xbounds, const int32_t *xkk, int xksize, int new_h, const int32_t *ybounds,
+                       const int32_t *ykk, int yksize, const int32_t *params, int ch, int cw, int strip_rows, const float *lut, int out_dtype,
+                       void *out, int out_pstride, int out_c0, int zero_pad_to, void *stream);
+
 /* hardware probes used by the GPU test-suite (MFMA fragment layouts, ds_read_b64_tr_b16 semantics) */
 int dl_probe_mfma16(const uint16_t *a /*16x32 bf16 row-major*/, const uint16_t *b /*32x16*/, float *d /*16x16*/, void *stream);
 int dl_probe_trread(const uint16_t *src /*64 rows x 16 cols bf16*/, uint16_t *dst /*64 lanes x 4*/, void *stream);
