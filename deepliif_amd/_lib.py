@@ -92,6 +92,8 @@ SIGNATURES = {
     'dl_pp_kde_first_minimum': (_i, [_vp, _i, _i, _vp, _vp]),
     'dl_pp_cells': (_i, [_vp, C.c_size_t, _vp, C.c_size_t, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
     'dl_pp_finish': (_i, [_vp, C.c_size_t, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, C.c_size_t, _vp, C.c_size_t, _vp]),
+    'dl_pp_outline_count': (_i, [_vp, _i, _i, _vp, _i, _i, _i, _vp, _vp]),
+    'dl_pp_outline_emit': (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _i64, _vp]),
     'dl_conv_forward_bnstats': (_i, [C.POINTER(ConvDesc), _vp, _vp, _vp, _vp, _vp, C.POINTER(ConvBnStats), _vp]),
     'dl_conv_kernel_name': (C.c_char_p, [C.POINTER(ConvDesc)]),
     'dl_conv_add_supported': (_i, [C.POINTER(ConvDesc)]),

@@ -345,6 +345,50 @@ extern "C" int dl_pp_finish(const void *orig, size_t orig_row_stride, void *mask
     return 0;
 }
 
+// ---------------------------------------------------------------------------------------------------- cell outlines
+// get_cell_boundary + make_simple_contour + encode_cell_data_v4 (:491-634, :752-848), one lane per cell; the trace, its bound and the two
+// lane functions are in outline.h (shared with the host check).  Lanes of a wavefront walk outlines of different lengths through
+// dependent byte loads: latency-bound and divergent by construction, one wavefront per workgroup so that the cells spread over the CUs.
+#include "outline.h"
+
+__global__ void __launch_bounds__(64) pp_outline_count_kernel(const uint8_t *mask, int H, int W, const int *cells, int n, int ox, int oy, int *counts) {
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    if (i < n) ppo_count_lane(mask, H, W, cells, i, ox, oy, counts);
+}
+__global__ void __launch_bounds__(64) pp_outline_emit_kernel(const uint8_t *mask, int H, int W, const int *cells, int *counts, const long long *offsets,
+                                                             int n, int ox, int oy, int mode, void *out, long long out_items) {
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    if (i < n) ppo_emit_lane(mask, H, W, cells, counts, offsets, i, ox, oy, mode, out, out_items);
+}
+
+static int ppo_check(const char *name, const void *mask, int H, int W, const void *cells, int n, const void *counts) {
+    if (H <= 0 || W <= 0 || (size_t)H * W >= ((size_t)1 << 31)) DL_FAIL("%s: empty problem or too large (H=%d W=%d)", name, H, W);
+    if (n < 0) DL_FAIL("%s: n=%d", name, n);
+    if (n > 0 && (!mask || !cells || !counts)) DL_FAIL("%s: null argument", name);
+    return 0;
+}
+
+extern "C" int dl_pp_outline_count(const void *mask, int H, int W, const int *cells, int n, int ox, int oy, int *counts, void *stream_) {
+    if (ppo_check("dl_pp_outline_count", mask, H, W, cells, n, counts)) return -1;
+    if (n == 0) return 0;
+    hipLaunchKernelGGL(pp_outline_count_kernel, dim3((n + 63) / 64), dim3(64), 0, (hipStream_t)stream_, (const uint8_t *)mask, H, W, cells, n, ox, oy, counts);
+    DL_CHECK_LAUNCH("dl_pp_outline_count");
+    return 0;
+}
+
+extern "C" int dl_pp_outline_emit(const void *mask, int H, int W, const int *cells, int *counts, const long long *offsets, int n, int ox, int oy,
+                                  int mode, void *out, long long out_items, void *stream_) {
+    if (ppo_check("dl_pp_outline_emit", mask, H, W, cells, n, counts)) return -1;
+    if (mode != DL_PP_OUTLINE_POINTS && mode != DL_PP_OUTLINE_STRINGS) DL_FAIL("dl_pp_outline_emit: mode=%d", mode);
+    if (out_items < 0 || (out_items > 0 && !out)) DL_FAIL("dl_pp_outline_emit: out_items=%lld with out=%p", out_items, out);
+    if (n == 0) return 0;
+    if (!offsets) DL_FAIL("dl_pp_outline_emit: null argument");
+    hipLaunchKernelGGL(pp_outline_emit_kernel, dim3((n + 63) / 64), dim3(64), 0, (hipStream_t)stream_, (const uint8_t *)mask, H, W, cells, counts, offsets,
+                       n, ox, oy, mode, out, out_items);
+    DL_CHECK_LAUNCH("dl_pp_outline_emit");
+    return 0;
+}
+
 // ---------------------------------------------------------------------------------------------------- host-only helper
 // calculate_default_size_threshold's kernel density estimate (postprocessing.py:365-447) over the cell list: count bins, bandwidth 1,
 // kde[i] = float32( sum_j exp(-((i*step - v_j)^2 / 2)) / sqrt(2 pi)  / n ), summed over j in list order in float64 -- the reference's

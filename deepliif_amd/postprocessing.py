@@ -7,6 +7,11 @@ dl_pp_finish).  What stays on the host is the arithmetic over the CELL LIST (hun
 rounding, the default size threshold (a 500-bin KDE of sqrt(size), :365-447, repeated expression by expression so that its float64
 comparisons agree) and the default marker threshold (:450-488, from a 256-bin histogram the GPU produces instead of np.percentile over
 the image).  There is no CPU fallback: without the HIP library this module raises.
+
+`compute_cell_results(seg, marker, resolution, version, ..., route=None, offset=(0, 0))` (:1136-1220) is the per-cell export: on top of the cell
+mapping, every cell's bounding box and simplified outline, as dicts (data versions 3 / 5) or base-92 + Freeman-chain strings (4 / 6).  The outlines are
+traced and encoded on the GPU (dl_pp_outline_count / dl_pp_outline_emit, one lane per cell; outline_cells below); the per-cell Python code the
+reference's functions translate to is kept as route='host', the yardstick.  `offset` places the image inside a slide (wsi.infer_slide_cells).
 """
 from __future__ import annotations
 
@@ -110,10 +115,11 @@ def calculate_default_marker_threshold(hist) -> int:
 class CellMap:
     """Device-side result of the cell mapping (get_cells_info, :311-362) plus the host-side cell list."""
 
-    def __init__(self, mask, label, ws, rows, keep, cells, defaults, shape):
+    def __init__(self, mask, label, ws, rows, keep, cells, defaults, shape, table=None):
         self.mask, self.label, self.ws = mask, label, ws          # uint8 [H][W], int32 [H][W], workspace shared with dl_pp_finish
         self.rows, self.keep = rows, keep                         # every component's reductions (int64 [n][8]); which of them are cells
         self.cells, self.defaults, self.shape = cells, defaults, shape
+        self.table = table                                        # `cells` as the int32 [n][8] rows of dl_pp_outline_* (outline_table)
 
 
 def get_cells_info(seg, marker, resolution, noise_thresh, seg_thresh, large_noise_thresh, use_od=False, device=None) -> CellMap:
@@ -164,7 +170,10 @@ def get_cells_info(seg, marker, resolution, noise_thresh, seg_thresh, large_nois
     defaults = {'size_thresh': calculate_default_size_threshold([c[0] for c in cells], resolution)}
     if hist_d is not None:
         defaults['marker_thresh'] = calculate_default_marker_threshold(hist_d.cpu().numpy())
-    return CellMap(mask, label, ws, rows, keep, cells, defaults, (H, W))
+    table = np.zeros((len(k), 8), dtype=np.int32)
+    for j, col in enumerate((k[:, 4], k[:, 5], kc, pos, mval, cx, cy)):
+        table[:, j] = col
+    return CellMap(mask, label, ws, rows, keep, cells, defaults, (H, W), table)
 
 
 def create_cell_classification(cm: CellMap, size_thresh=0, marker_thresh=None, size_thresh_upper=None, od_thresh_lower=None, od_thresh_upper=None):
@@ -228,9 +237,11 @@ def compute_final_results(orig, seg, marker, resolution, size_thresh='default', 
 
 
 # ---------------------------------------------------------------------------------------------------------------
-# Per-cell export (compute_cell_results, postprocessing.py:1136-1220): host code over the label mask the GPU produced.  Boundary
-# tracing is pointer chasing along each cell's outline (a few dozen steps per cell); the "v4" strings are DeepLIIF's wire format
-# for cell lists (base-92 numbers + Freeman chain code), so their layout below is a contract, not a choice.
+# Per-cell export (compute_cell_results, postprocessing.py:1136-1220).  The "v4" strings are DeepLIIF's wire format for cell lists
+# (base-92 numbers + Freeman chain code), so their layout below is a contract, not a choice.  The functions from here to
+# cell_results_from_mapping are the HOST route: pure Python over a host copy of the label mask, a few hundred microseconds per cell --
+# the yardstick the outline kernels (dl_pp_outline_count / dl_pp_outline_emit, route 'gpu' of compute_cell_results) are held to, byte
+# for byte, and not what a slide runs through.
 # ---------------------------------------------------------------------------------------------------------------
 _RING = ((-1, -1), (0, -1), (1, -1), (1, 0), (1, 1), (0, 1), (-1, 1), (-1, 0))        # (dx, dy), clockwise from the upper-left neighbour
 _RING_INDEX = {d: i for i, d in enumerate(_RING)}
@@ -348,31 +359,182 @@ def encode_cell_data_v4(data, v6=False):
     return head + body + ''.join(chain)
 
 
-def cell_results_from_mapping(mask, cells, defaults, version, seg_thresh, noise_thresh, large_noise_thresh):
+_FREEMAN_STEP = {code: step for step, code in _FREEMAN.items()}
+
+
+def decode_cell_data_v4(cell, v6=False):
+    """postprocessing.py:851-920, the inverse of encode_cell_data_v4: the lengths byte gives the three widths, the numbers follow in the
+    order of the layout above, then every chain character moves `steps` pixels in its direction from the last point.  A character that
+    repeats the direction of the one before it (a run longer than 10 steps) extends that point instead of adding one."""
+    n = ord(cell[0]) - 35
+    w_size, w_tl, w_off = n // 16 + 1, (n // 4) % 4 + 1, n % 4 + 1
+    pos = 1
+
+    def take(width):
+        nonlocal pos
+        pos += width
+        return from_base92(cell[pos - width:pos])
+
+    size = take(w_size)
+    cls = take(2)
+    ax, ay = take(w_tl), take(w_tl)
+    offs = [take(w_off) for _ in range(6)]
+    pts = [(ax + offs[4], ay + offs[5])]
+    last = None
+    for ch in cell[pos:]:
+        steps, code = divmod(ord(ch) - 35, 8)
+        dx, dy = _FREEMAN_STEP[code]
+        nxt = (pts[-1][0] + dx * steps, pts[-1][1] + dy * steps)
+        if code == last:
+            pts[-1] = nxt
+        else:
+            pts.append(nxt)
+        last = code
+    return {'size': size, 'positive': bool(cls % 2), ('od' if v6 else 'marker'): cls // 2, 'bbox': [(ax, ay), (ax + offs[0], ay + offs[1])],
+            'centroid': (ax + offs[2], ay + offs[3]), 'boundary': pts}
+
+
+def shift_cell(data, offset):
+    """models/__init__.py:892-896: a decoded cell moved by the offset of its region inside the slide"""
+    ox, oy = offset
+    out = dict(data)
+    out['bbox'] = [(x + ox, y + oy) for x, y in data['bbox']]
+    out['centroid'] = (data['centroid'][0] + ox, data['centroid'][1] + oy)
+    out['boundary'] = [(x + ox, y + oy) for x, y in data['boundary']]
+    return out
+
+
+def _cell_settings(defaults, version, seg_thresh, noise_thresh, large_noise_thresh):
+    settings = {'default_size_thresh': defaults['size_thresh'], 'noise_thresh': noise_thresh, 'large_noise_thresh': large_noise_thresh,
+                'seg_thresh': seg_thresh}
+    if version not in (5, 6):
+        settings['default_marker_thresh'] = defaults['marker_thresh'] if 'marker_thresh' in defaults else None
+    return settings
+
+
+def cell_results_from_mapping(mask, cells, defaults, version, seg_thresh, noise_thresh, large_noise_thresh, offset=(0, 0)):
     """The host half of compute_cell_results (:1170-1220): per-cell boundary, bbox and (for versions 4 / 6) the encoded string.
-    mask: 2-D uint8 ndarray after the cell mapping (0 = background), cells / defaults as get_cells_info returns them."""
+    mask: 2-D uint8 ndarray after the cell mapping (0 = background), cells / defaults as get_cells_info returns them.  With an offset
+    every cell is moved before it is encoded (what models/__init__.py:883-903 reaches by decode -> shift -> encode)."""
     od = version in (5, 6)
     out = []
     for c in cells:
         bbox, boundary = get_cell_boundary(mask, c[3], c[4])
         data = {'size': c[0], 'positive': c[1], ('od' if od else 'marker'): c[2], 'bbox': bbox, 'centroid': (c[5], c[6]),
                 'boundary': make_simple_contour(boundary)}
+        if tuple(offset) != (0, 0):
+            data = shift_cell(data, offset)
         out.append(encode_cell_data_v4(data, v6=(version == 6)) if version in (4, 6) else data)
-    settings = {'default_size_thresh': defaults['size_thresh'], 'noise_thresh': noise_thresh, 'large_noise_thresh': large_noise_thresh,
-                'seg_thresh': seg_thresh}
-    if not od:
-        settings['default_marker_thresh'] = defaults['marker_thresh'] if 'marker_thresh' in defaults else None
-    return {'cells': out, 'settings': settings, 'dataVersion': version}
+    return {'cells': out, 'settings': _cell_settings(defaults, version, seg_thresh, noise_thresh, large_noise_thresh), 'dataVersion': version}
+
+
+OUTLINE_STATUS = {1: 'its first pixel lies outside the image', 2: 'its first pixel is background',
+                  3: 'the outline did not close within 8 * size + 8 moves (the size is not that of the cell at the first pixel)'}
+
+
+def outline_table(cells) -> np.ndarray:
+    """get_cells_info's cell list [(size, positive, value, first x, first y, centre x, centre y)] -> the int32 [n][8] rows of
+    dl_pp_outline_*: {first x, first y, size, positive, value, centre x, centre y, 0}"""
+    t = np.zeros((len(cells), 8), dtype=np.int32)
+    if len(cells):
+        a = np.asarray(cells, dtype=np.int64).reshape(len(cells), 7)
+        t[:, :7] = a[:, [3, 4, 0, 1, 2, 5, 6]]
+    return t
+
+
+def outline_cells(mask, cells, version, offset=(0, 0), timings=None, lib=None):
+    """The cells of compute_cell_results (:1170-1220) from the DEVICE mask: dl_pp_outline_count (bbox, kept points, string length per
+    cell), an exclusive scan of those on the host (numpy), dl_pp_outline_emit (the kept points, or the complete strings in one byte
+    buffer).  mask: uint8 [H][W] CUDA tensor, 0 = background; cells: get_cells_info's list or an outline_table().  -> list of dicts
+    (versions 3 / 5) or strings (4 / 6), moved by `offset`.  A cell the kernel refuses (OUTLINE_STATUS) raises.
+    timings (dict, optional): seconds spent after the last device->host copy, i.e. building the Python objects ('python');
+    lib: the library to call (default: the one of the current 16-bit format; the kernels are the same in both builds)."""
+    import time
+    lib = lib if lib is not None else ops.impl().lib
+    if not (isinstance(mask, torch.Tensor) and mask.is_cuda and mask.dtype == torch.uint8 and mask.dim() == 2 and mask.is_contiguous()):
+        raise ValueError('outline_cells: the mask must be a contiguous uint8 [H][W] CUDA tensor')
+    table = cells if isinstance(cells, np.ndarray) else outline_table(cells)
+    if table.dtype != np.int32 or table.ndim != 2 or table.shape[1] != 8:
+        raise ValueError('outline_cells: the cell table must be int32 [n][8]')
+    n = int(table.shape[0])
+    if n == 0:
+        return []
+    H, W = int(mask.shape[0]), int(mask.shape[1])
+    ox, oy = int(offset[0]), int(offset[1])
+    strings = version in (4, 6)
+    dev = mask.device
+    p, stream = ops._ptr, ops._stream(mask)
+    table_d = torch.from_numpy(np.ascontiguousarray(table)).to(dev)
+    counts_d = torch.empty((n, 8), dtype=torch.int32, device=dev)
+    L.check(lib.dl_pp_outline_count(p(mask), H, W, p(table_d), n, ox, oy, p(counts_d), stream), 'dl_pp_outline_count', lib)
+    counts = counts_d.cpu().numpy()
+    bad = np.flatnonzero(counts[:, 0])
+    if len(bad):
+        i = int(bad[0])
+        raise RuntimeError(f'dl_pp_outline_count: status {int(counts[i, 0])} for cell {i} (first pixel ({int(table[i, 0])}, {int(table[i, 1])}), size '
+                           f'{int(table[i, 2])}) of {n}: {OUTLINE_STATUS.get(int(counts[i, 0]), "unknown status")}; {len(bad)} cells refused')
+    items = counts[:, 6 if strings else 5].astype(np.int64)
+    offsets = np.zeros(n + 1, dtype=np.int64)
+    np.cumsum(items, out=offsets[1:])
+    total = int(offsets[-1])
+    out_d = torch.empty(total, dtype=torch.uint8, device=dev) if strings else torch.empty((total, 2), dtype=torch.int32, device=dev)
+    offsets_d = torch.from_numpy(offsets).to(dev)
+    L.check(lib.dl_pp_outline_emit(p(mask), H, W, p(table_d), p(counts_d), p(offsets_d), n, ox, oy, 1 if strings else 0, p(out_d), total, stream),
+            'dl_pp_outline_emit', lib)
+    stored = counts_d[:, 7].cpu().numpy()
+    if not np.array_equal(stored, items):
+        i = int(np.flatnonzero(stored != items)[0])
+        raise RuntimeError(f'dl_pp_outline_emit: cell {i} produced {int(stored[i])} items, the count pass {int(items[i])} (the mask changed between the passes?)')
+    out = out_d.cpu().numpy()
+    t0 = time.perf_counter()
+    if strings:
+        blob = out.tobytes().decode('ascii')
+        offs = offsets.tolist()
+        res = [blob[a:b] for a, b in zip(offs[:-1], offs[1:])]
+    else:
+        # two bulk conversions: the per-cell rows (moved by the offset in numpy) and every kept point of every cell
+        rows = np.empty((n, 11), dtype=np.int64)
+        rows[:, 0], rows[:, 1], rows[:, 2] = table[:, 2], table[:, 3], table[:, 4]
+        rows[:, 3:7] = counts[:, 1:5].astype(np.int64) + np.array([ox, oy, ox, oy], dtype=np.int64)
+        rows[:, 7], rows[:, 8] = table[:, 5].astype(np.int64) + ox, table[:, 6].astype(np.int64) + oy
+        rows[:, 9], rows[:, 10] = offsets[:-1], offsets[1:]
+        # (a million small tuples and lists: the cyclic collector, which would rescan them again and again while they are made, waits)
+        import gc
+        pause = gc.isenabled()
+        if pause:
+            gc.disable()
+        try:
+            flat = out.ravel().tolist()
+            pts = list(zip(flat[0::2], flat[1::2]))
+            key = 'od' if version in (5, 6) else 'marker'
+            res = [{'size': size, 'positive': bool(positive), key: value, 'bbox': [(x0, y0), (x1, y1)], 'centroid': (cx, cy), 'boundary': pts[a:b]}
+                   for size, positive, value, x0, y0, x1, y1, cx, cy, a, b in rows.tolist()]
+        finally:
+            if pause:
+                gc.enable()
+    if timings is not None:
+        timings['python'] = timings.get('python', 0.0) + (time.perf_counter() - t0)
+    return res
 
 
 def compute_cell_results(seg, marker, resolution, version=3, seg_thresh=DEFAULT_SEG_THRESH, noise_thresh=DEFAULT_NOISE_THRESH,
-                         large_noise_thresh=None, device=None):
+                         large_noise_thresh=None, device=None, route=None, offset=(0, 0)):
     """deepliif/postprocessing.py:1136-1220: individual cell data.  Versions 3 / 4 take the inferred marker image, 5 / 6 the ORIGINAL image
-    (optical density); 4 / 6 return every cell as one encoded ASCII string."""
+    (optical density); 4 / 6 return every cell as one encoded ASCII string.
+    route: 'gpu' = outline_cells (the label mask stays on the device), 'host' = cell_results_from_mapping on a host copy of the mask (the
+    yardstick), None = 'gpu' when the library exports the outline kernels, else 'host'.  offset: position of this image inside a slide
+    (infer_cells_for_wsi, models/__init__.py:883-903), added to every coordinate; (0, 0) is the reference's compute_cell_results."""
     import warnings
     if version not in (3, 4, 5, 6):
         warnings.warn('Invalid cell data version provided, defaulting to version 3.')
         version = 3
+    if route is None:
+        route = 'gpu' if hasattr(ops.impl().lib, 'dl_pp_outline_emit') else 'host'
+    if route not in ('gpu', 'host'):
+        raise ValueError(f"unknown route {route!r} ('gpu' | 'host')")
     large = calculate_large_noise_thresh(large_noise_thresh, resolution)
     cm = get_cells_info(seg, marker, resolution, noise_thresh, seg_thresh, large, use_od=version in (5, 6), device=device)
-    return cell_results_from_mapping(cm.mask.cpu().numpy(), cm.cells, cm.defaults, version, seg_thresh, noise_thresh, large)
+    if route == 'host':
+        return cell_results_from_mapping(cm.mask.cpu().numpy(), cm.cells, cm.defaults, version, seg_thresh, noise_thresh, large, offset=offset)
+    cells = outline_cells(cm.mask, cm.table, version, offset)
+    return {'cells': cells, 'settings': _cell_settings(cm.defaults, version, seg_thresh, noise_thresh, large), 'dataVersion': version}

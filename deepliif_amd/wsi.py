@@ -16,7 +16,10 @@ a deterministic assignment with no collective on the data path:
     (tiling.split_rows); the bands of a region are reassembled (inference.gather_bands) before its post-processing, which needs the whole
     region.
 File I/O stays outside (bioformats / tiff writers are out of scope): the caller passes read_region(x, y, w, h) -> uint8 [h, w, 3]
-and receives per-region results to paste / write; paste_into() does the reference's canvas paste."""
+and receives per-region results to paste / write; paste_into() does the reference's canvas paste.
+
+infer_slide_cells() / merge_cell_results() are the same schedule for deepliif.models.infer_cells_for_wsi (:785-947), the slide's individual cell
+data: its own region grid (cell_region_grid), seg_only inference, compute_cell_results with the region's offset."""
 from __future__ import annotations
 
 from dataclasses import dataclass
@@ -36,6 +39,16 @@ def region_grid(size_x: int, size_y: int, region_size: int = 20000) -> List[Tupl
     return out
 
 
+def cell_region_grid(size_x: int, size_y: int, region_size: int = 20000) -> List[Tuple[int, int, int, int]]:
+    """(x, y, w, h) of every region of infer_cells_for_wsi (models/__init__.py:828-922), which is NOT region_grid(): the slide is cut into
+    ceil(size / region_size) regions per axis of EQUAL stride ceil(size / n) (the last one takes what is left), start_y outer loop, start_x inner."""
+    if size_x <= 0 or size_y <= 0 or region_size <= 0:
+        raise ValueError(f'empty slide or region ({size_x} x {size_y}, region {region_size})')
+    nx, ny = -(-size_x // region_size), -(-size_y // region_size)
+    stride_x, stride_y = -(-size_x // nx), -(-size_y // ny)
+    return [(x, y, min(stride_x, size_x - x), min(stride_y, size_y - y)) for y in range(0, size_y, stride_y) for x in range(0, size_x, stride_x)]
+
+
 @dataclass(frozen=True)
 class RegionJob:
     index: int                       # position in region_grid() order
@@ -53,9 +66,11 @@ class SlidePlan:
     tiles_per_rank: List[int]
 
 
-def plan_slide(size_x: int, size_y: int, tile_size: int, world: int = 1, region_size: int = 20000, overlap_size: Optional[int] = None) -> SlidePlan:
+def plan_slide(size_x: int, size_y: int, tile_size: int, world: int = 1, region_size: int = 20000, overlap_size: Optional[int] = None,
+               regions: Optional[List[Tuple[int, int, int, int]]] = None) -> SlidePlan:
+    """regions: the (x, y, w, h) list to schedule (default region_grid(); infer_slide_cells passes cell_region_grid())"""
     overlap = tile_size // 16 if overlap_size is None else overlap_size          # infer_modalities' overlap (models/__init__.py:632)
-    regions = region_grid(size_x, size_y, region_size)
+    regions = region_grid(size_x, size_y, region_size) if regions is None else list(regions)
     plans = [TilePlan(w, h, tile_size, overlap) for (_, _, w, h) in regions]
     counts = [len(p.ys) * len(p.xs) for p in plans]
     jobs: List[List[RegionJob]] = [[] for _ in range(world)]
@@ -152,3 +167,80 @@ def infer_slide(read_region: Callable[[int, int, int, int], 'object'], size_x: i
         if on_region is not None:
             on_region(job.xywh, images, scoring)
     return plan, total
+
+
+def infer_slide_cells(read_region: Callable[[int, int, int, int], 'object'], size_x: int, size_y: int, tile_size: int, model_dir: Optional[str] = None, *,
+                      version: int = 3, region_size: int = 20000, seg_weights=None, nets=None, opt=None, rank: int = 0, world: int = 1, batch_size: int = 8,
+                      on_region: Optional[Callable[[Tuple[int, int, int, int], dict], None]] = None):
+    """This rank's share of deepliif.models.infer_cells_for_wsi (models/__init__.py:785-947): the individual cell data of a slide.  Per region
+    of cell_region_grid(): inference(seg_only=True, overlap tile_size // 16) -> compute_cell_results on the Seg image and the *Marker image
+    (data versions 3 / 4) or the region itself (5 / 6, optical density), with offset = the region's position, so that the cells come out in slide
+    coordinates (the reference decodes, shifts and encodes every cell again, :883-903; the outline kernels add the offset while they encode).
+    Regions go to ranks as in infer_slide (plan_slide): whole regions, or -- fewer regions than ranks -- bands of every region through
+    inference(rank=, world=) with the cells computed on rank 0.
+    Returns (plan, [(region index, region data)] of the regions THIS rank computed); merge_cell_results() joins the parts of all ranks."""
+    import numpy as np
+    from PIL import Image
+    from . import inference as I
+    from . import postprocessing as PP
+    plan = plan_slide(size_x, size_y, tile_size, world, region_size, regions=cell_region_grid(size_x, size_y, region_size))
+    resolution = '40x' if tile_size > 384 else ('20x' if tile_size > 192 else '10x')          # models/__init__.py:817
+    if opt is None and model_dir is not None:
+        opt = I.get_opt(model_dir)
+    parts = []
+    for job in plan.jobs[rank]:
+        x, y, w, h = job.xywh
+        region = read_region(x, y, w, h)
+        if hasattr(region, 'is_cuda'):
+            region = region.cpu().numpy()
+        img = region if isinstance(region, Image.Image) else Image.fromarray(np.ascontiguousarray(np.asarray(region, dtype=np.uint8)))
+        images = I.inference(img, tile_size=tile_size, overlap_size=tile_size // 16, model_path=model_dir, eager_mode=False, color_dapi=False,
+                             color_marker=False, opt=opt, return_seg_intermediate=False, seg_only=True, seg_weights=seg_weights, nets=nets,
+                             batch_size=batch_size, rank=job.rank, world=job.world)
+        if images is None:          # 'bands' mode, rank != 0
+            continue
+        if version in (5, 6):
+            marker = img
+        else:
+            key = I.find_marker_key(images)
+            marker = images[key] if key is not None else None
+        data = PP.compute_cell_results(images['Seg'], marker, resolution, version=version, offset=(x, y))
+        parts.append((job.index, data))
+        if on_region is not None:
+            on_region(job.xywh, data)
+    return plan, parts
+
+
+def merge_cell_results(parts_in_region_order, tile_size: int, region_size: int = 20000, seg_weights=None, model_dir: Optional[str] = None) -> dict:
+    """models/__init__.py:905-947: the region results (compute_cell_results dicts, in cell_region_grid() order) as one: cells concatenated; the
+    settings of the first region with default_marker_thresh (versions 3 / 4; over the regions where it is neither None nor 0) and
+    default_size_thresh (where it is not 0) replaced by round(sum / max(count, 1)) -- Python's round, half to even; tile_size, region_size,
+    seg_weights; the installed deepliif version and the model directory's name."""
+    import importlib.metadata
+    import pathlib
+    parts = list(parts_in_region_order)
+    if not parts:
+        raise ValueError('merge_cell_results: no region results')
+    version = parts[0]['dataVersion']
+    data = {'cells': [], 'settings': dict(parts[0]['settings']), 'dataVersion': version}
+    marker_sum = marker_n = size_sum = size_n = 0
+    for part in parts:
+        data['cells'] += part['cells']
+        st = part['settings']
+        if version in (3, 4) and st['default_marker_thresh'] is not None and st['default_marker_thresh'] != 0:
+            marker_sum, marker_n = marker_sum + st['default_marker_thresh'], marker_n + 1
+        if st['default_size_thresh'] != 0:
+            size_sum, size_n = size_sum + st['default_size_thresh'], size_n + 1
+    if version in (3, 4):
+        data['settings']['default_marker_thresh'] = round(marker_sum / max(marker_n, 1))
+    data['settings']['default_size_thresh'] = round(size_sum / max(size_n, 1))
+    data['settings']['tile_size'], data['settings']['region_size'], data['settings']['seg_weights'] = tile_size, region_size, seg_weights
+    try:
+        data['deepliifVersion'] = importlib.metadata.version('deepliif')
+    except Exception:
+        data['deepliifVersion'] = 'unknown'
+    try:
+        data['modelVersion'] = pathlib.PurePath(model_dir).name
+    except Exception:
+        data['modelVersion'] = 'unknown'
+    return data

@@ -597,6 +597,33 @@ int dl_pp_kde_first_minimum(const double *values, int n, int count, double *step
 int dl_pp_finish(const void *orig, size_t orig_row_stride, void *mask, const int *label, const void *ws, const void *code, int n_cells,
                  int H, int W, void *overlay, size_t overlay_row_stride, void *refined, size_t refined_row_stride, void *stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * Cell outlines (deepliif/postprocessing.py: get_cell_boundary :491-581, make_simple_contour :584-634, encode_cell_data_v4 :752-848, as
+ * driven by compute_cell_results :1136-1220 and, with a region offset, by infer_cells_for_wsi, models/__init__.py:883-903).  One lane per
+ * cell, two passes over the same Moore-neighbour trace; the simplification and the chain code run as a stream over the trace.
+ *   mask   uint8 [H][W], contiguous, 0 = background (dl_pp_cells' mask),
+ *   cells  int32 [n][8] (device): {first x, first y, size, positive, marker / optical-density value, centroid x, centroid y, 0},
+ *   counts int32 [n][8] (device): {status, min x, min y, max x, max y, kept points, string length, items the emit pass stored};
+ *          status DL_PP_OUTLINE_OK, _OUTSIDE (first pixel not in the image), _BACKGROUND (first pixel is background), _OPEN (the trace
+ *          did not close within 8 * size + 8 moves: `size` is not the size of the cell at `first`).  A cell with a status != OK has
+ *          zero points and zero length and is skipped by the emit pass; nothing outside the image is read.
+ *   (ox, oy): offset of the image inside the slide, added to every coordinate that is stored (the bbox corner BEFORE its digit width
+ *          is chosen; the six offsets of the string are differences and do not move).
+ * dl_pp_outline_count fills counts[.][0..6].  dl_pp_outline_emit, with offsets int64 [n + 1] (device) = the exclusive scan of the
+ * kept points (mode DL_PP_OUTLINE_POINTS: out = int32 [out_items][2], x + ox, y + oy) or of the string lengths (mode
+ * DL_PP_OUTLINE_STRINGS: out = char [out_items], every cell's complete encode_cell_data_v4 string), stores cell i inside
+ * [offsets[i], min(offsets[i + 1], out_items)) and nothing else, and sets counts[i][7] to the number of items it produced.
+ * ---------------------------------------------------------------------------------------------------------- */
+#define DL_PP_OUTLINE_OK 0
+#define DL_PP_OUTLINE_OUTSIDE 1
+#define DL_PP_OUTLINE_BACKGROUND 2
+#define DL_PP_OUTLINE_OPEN 3
+#define DL_PP_OUTLINE_POINTS 0
+#define DL_PP_OUTLINE_STRINGS 1
+int dl_pp_outline_count(const void *mask, int H, int W, const int *cells, int n, int ox, int oy, int *counts, void *stream);
+int dl_pp_outline_emit(const void *mask, int H, int W, const int *cells, int *counts, const long long *offsets, int n, int ox, int oy,
+                       int mode, void *out, long long out_items, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
