@@ -69,6 +69,11 @@ class NormDesc(C.Structure):
                 ('dtype', i32), ('scope', i32), ('act', i32), ('eps', C.c_float), ('momentum', C.c_float), ('ext_nchunks', i32)]
 
 
+class RenderThresh(C.Structure):     # dl_pp_render_thresh
+    _fields_ = [('size_lower', C.c_int64), ('size_upper', C.c_int64), ('marker', C.c_int64), ('od_lower', C.c_int64), ('od_upper', C.c_int64),
+                ('has_size_upper', i32), ('has_marker', i32), ('has_od_lower', i32), ('has_od_upper', i32)]
+
+
 class DropoutDesc(C.Structure):      # dl_dropout_desc
     _fields_ = [('p', C.c_float), ('seed', C.c_uint64), ('seed_dev', C.c_void_p), ('call_index', C.c_uint32)]
 
@@ -94,6 +99,10 @@ SIGNATURES = {
     'dl_pp_finish': (_i, [_vp, C.c_size_t, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, C.c_size_t, _vp, C.c_size_t, _vp]),
     'dl_pp_outline_count': (_i, [_vp, _i, _i, _vp, _i, _i, _i, _vp, _vp]),
     'dl_pp_outline_emit': (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _i64, _vp]),
+    'dl_pp_render_count': (_i, [_i, _i, _vp, _i64, _vp, _vp, _i, _vp, _i, _i, _i, _i, _vp, _vp]),
+    'dl_pp_render_paint': (_i, [_i, _vp, _i64, _vp, _i, _vp, _i, _i, _i, _i, _vp, _vp]),
+    'dl_pp_render_ws_bytes': (C.c_size_t, [_i, _i]),
+    'dl_pp_render_finish': (_i, [_vp, C.c_size_t, _vp, _vp, _i, _vp, _i, _i, _vp, C.c_size_t, _vp, C.c_size_t, _vp]),
     'dl_conv_forward_bnstats': (_i, [C.POINTER(ConvDesc), _vp, _vp, _vp, _vp, _vp, C.POINTER(ConvBnStats), _vp]),
     'dl_conv_kernel_name': (C.c_char_p, [C.POINTER(ConvDesc)]),
     'dl_conv_add_supported': (_i, [C.POINTER(ConvDesc)]),
@@ -187,7 +196,11 @@ def load(half: str = 'bf16'):
             f'(or `make -C deepliif_amd/csrc`). deepliif_amd has no CPU / PyTorch fallback.')
     lib = C.CDLL(path)
     for name, (res, args) in SIGNATURES.items():
-        fn = getattr(lib, name)           # AttributeError if the .so does not export a declared symbol
+        try:
+            fn = getattr(lib, name)
+        except AttributeError:            # the .so does not export a declared symbol: built from older sources
+            raise HipLibraryError(f'{os.path.basename(path)} does not export {name} (stale build, version {lib.dl_version()}): rebuild it with '
+                                  f'`make -C deepliif_amd/csrc`') from None
         fn.restype = res
         fn.argtypes = args
     if lib.dl_version() != DL_VERSION:

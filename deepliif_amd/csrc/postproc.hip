@@ -389,6 +389,180 @@ extern "C" int dl_pp_outline_emit(const void *mask, int H, int W, const int *cel
     return 0;
 }
 
+// ---------------------------------------------------------------------------------------------------- rendering a stored cell list
+// cells_to_final_results (:1307-1412).  The reference paints outlines cell by cell into a label map and runs four in-place raster
+// passes over it; what they compute is order-free:
+//   * an outline pixel belongs to the LAST counted cell of the list that covers it           -> atomicMax of the cell index (owner map);
+//   * background = the 4-connected UNKNOWN components that hold an image-border pixel        -> the union-find passes of dl_pp_cells;
+//   * fill_cells: a run of UNKNOWN pixels in a row is POSITIVE iff the pixel left of it is BORDER_POS (the raster loop carries that
+//     one bit along the run)                                                                -> ballots per 64 pixels + a carried bit;
+//   * create_outer_boundary: a BACKGROUND pixel takes the border label of its first POSITIVE / NEGATIVE neighbour in the order up,
+//     left, right, down = the first WRITER in raster order; written labels are border labels and write nothing themselves -> a gather;
+//   * enlarge_cell_boundaries / create_final_images: the kernels of dl_pp_finish.
+// The decode, count and paint lane functions are in render.h (shared with the host check).
+#include "render.h"
+
+__global__ void __launch_bounds__(64) pp_render_count_kernel(int mode, int v6, const void *data, long long data_items, const long long *offsets,
+                                                             const int *table, int n, dl_pp_render_thresh t, int ox, int oy, int H, int W, int *rows) {
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    if (i < n) ppr_count_lane(mode, v6, data, data_items, offsets, table, i, t, ox, oy, H, W, rows);
+}
+
+struct PPROwnerSink {
+    int *owner; int H, W, i;
+    __device__ __forceinline__ void pixel(int x, int y) {
+        if ((unsigned)x < (unsigned)W && (unsigned)y < (unsigned)H) atomicMax(owner + (size_t)y * W + x, i);
+    }
+};
+__global__ void __launch_bounds__(64) pp_render_paint_kernel(int mode, const void *data, long long data_items, const long long *offsets, int n,
+                                                             const int *rows, int ox, int oy, int H, int W, int *owner) {
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= n) return;
+    PPROwnerSink s{owner, H, W, i};
+    ppr_paint_lane(mode, data, data_items, offsets, rows, i, ox, oy, H, W, s);
+}
+
+// owner map -> UNKNOWN / BORDER_POS / BORDER_NEG + the initial labels of the UNKNOWN pixels for the background pass (as pp_mask_kernel)
+__global__ void __launch_bounds__(256) pp_render_mask_kernel(const int *owner, const int *rows, int n_cells, int H, int W, uint8_t *mask, int *label) {
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    const bool in = p < H * W;
+    uint8_t m = PP_BACKGROUND;
+    if (in) {
+        const int c = owner[p];
+        m = (c < 0 || c >= n_cells) ? PP_UNKNOWN : (rows[(size_t)c * 8 + 1] == 1 ? PP_BORDER_POS : PP_BORDER_NEG);
+    }
+    const int head = pp_run_head(in && m == PP_UNKNOWN, p, in ? p % W : 1);
+    if (!in) return;
+    mask[p] = m;
+    label[p] = head;
+}
+
+// fill_cells (:1075-1099), in place: one wavefront per row, 64 pixels at a time.  An UNKNOWN pixel takes the class of the nearest pixel
+// to its left that is not UNKNOWN (BORDER_POS -> POSITIVE, anything else -> NEGATIVE): inside the chunk that pixel is found with a ballot and
+// a count of leading zeros, beyond the chunk's left edge it is the bit carried from the chunks before (false at the start of a row).
+__global__ void __launch_bounds__(256) pp_render_fill_kernel(uint8_t *mask, int H, int W) {
+    const int y = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (y >= H) return;                                                // (a whole wavefront leaves)
+    uint8_t *row = mask + (size_t)y * W;
+    bool carry = false;
+    for (int x0 = 0; x0 < W; x0 += 64) {
+        const int x = x0 + lane;
+        const bool in = x < W;
+        const uint8_t m = in ? row[x] : PP_BACKGROUND;
+        const unsigned long long known = ~__ballot(in && m == PP_UNKNOWN), bpos = __ballot(in && m == PP_BORDER_POS);
+        const unsigned long long upto = known & (lane == 63 ? ~0ull : ((1ull << (lane + 1)) - 1));      // known pixels at or left of this lane
+        const bool pos = upto ? ((bpos >> (63 - __builtin_clzll(upto))) & 1) != 0 : carry;
+        if (in) {
+            uint8_t o = m;
+            if (m == PP_UNKNOWN) o = pos ? PP_POSITIVE : PP_NEGATIVE;
+            else if (m == PP_BORDER_POS) o = PP_POSITIVE;
+            else if (m == PP_BORDER_NEG) o = PP_NEGATIVE;
+            if (o != m) row[x] = o;
+        }
+        // what the last pixel of the chunk hands on (only full chunks have a successor; lanes beyond the row count as known, not BORDER_POS)
+        carry = known ? ((bpos >> (63 - __builtin_clzll(known))) & 1) != 0 : carry;
+    }
+}
+
+// create_outer_boundary (:1103-1122): a gather from the filled mask
+__global__ void __launch_bounds__(256) pp_render_boundary_kernel(const uint8_t *in, int H, int W, uint8_t *out) {
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    if (p >= H * W) return;
+    uint8_t o = in[p];
+    if (o == PP_BACKGROUND) {
+        const int y = p / W, x = p - y * W;
+        const int qs[4] = {y > 0 ? p - W : -1, x > 0 ? p - 1 : -1, x + 1 < W ? p + 1 : -1, y + 1 < H ? p + W : -1};      // up, left, right, down
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            if (qs[k] < 0 || o != PP_BACKGROUND) continue;
+            const uint8_t v = in[qs[k]];
+            if (v == PP_POSITIVE) o = PP_BORDER_POS;
+            else if (v == PP_NEGATIVE) o = PP_BORDER_NEG;
+        }
+    }
+    out[p] = o;
+}
+
+static int ppr_check(const char *name, int mode, const void *data, long long data_items, const void *offsets, int n, const void *rows, int H, int W) {
+    if (H <= 0 || W <= 0 || (size_t)H * W >= ((size_t)1 << 31)) DL_FAIL("%s: empty problem or too large (H=%d W=%d)", name, H, W);
+    if (n < 0) DL_FAIL("%s: n=%d", name, n);
+    if (mode != DL_PP_OUTLINE_POINTS && mode != DL_PP_OUTLINE_STRINGS) DL_FAIL("%s: mode=%d", name, mode);
+    if (data_items < 0 || (data_items > 0 && !data)) DL_FAIL("%s: data_items=%lld with data=%p", name, data_items, data);
+    if (n > 0 && (!offsets || !rows)) DL_FAIL("%s: null argument", name);
+    return 0;
+}
+
+extern "C" int dl_pp_render_count(int mode, int v6, const void *data, long long data_items, const long long *offsets, const int *table, int n,
+                                  const dl_pp_render_thresh *thresh, int ox, int oy, int H, int W, int *rows, void *stream_) {
+    if (ppr_check("dl_pp_render_count", mode, data, data_items, offsets, n, rows, H, W)) return -1;
+    if (!thresh) DL_FAIL("dl_pp_render_count: null argument");
+    if (n == 0) return 0;
+    if (mode == DL_PP_OUTLINE_POINTS && !table) DL_FAIL("dl_pp_render_count: the points mode needs the per-cell table");
+    hipLaunchKernelGGL(pp_render_count_kernel, dim3((n + 63) / 64), dim3(64), 0, (hipStream_t)stream_, mode, v6, data, data_items, offsets, table, n,
+                       *thresh, ox, oy, H, W, rows);
+    DL_CHECK_LAUNCH("dl_pp_render_count");
+    return 0;
+}
+
+extern "C" int dl_pp_render_paint(int mode, const void *data, long long data_items, const long long *offsets, int n, const int *rows, int ox, int oy,
+                                  int H, int W, int *owner, void *stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (ppr_check("dl_pp_render_paint", mode, data, data_items, offsets, n, rows, H, W)) return -1;
+    if (!owner) DL_FAIL("dl_pp_render_paint: null argument");
+    if (hipMemsetAsync(owner, 0xFF, (size_t)H * W * 4, stream) != hipSuccess) DL_FAIL("dl_pp_render_paint: memset");
+    if (n == 0) return 0;
+    hipLaunchKernelGGL(pp_render_paint_kernel, dim3((n + 63) / 64), dim3(64), 0, stream, mode, data, data_items, offsets, n, rows, ox, oy, H, W, owner);
+    DL_CHECK_LAUNCH("dl_pp_render_paint");
+    return 0;
+}
+
+// workspace of dl_pp_render_finish (bytes, regions 256-byte aligned): flag | label (int32[HW] each)  mask a | mask b (u8[HW] each) --
+// about 10 bytes per pixel, a quarter of what the cell mapping needs (dl_pp_ws_bytes)
+struct PPRLayout { size_t flag, label, m1, m2, total; };
+static void ppr_layout(int H, int W, PPRLayout *l) {
+    const size_t hw = (size_t)H * W;
+    size_t off = 0;
+    l->flag = off; off += pp_align(hw * 4);
+    l->label = off; off += pp_align(hw * 4);
+    l->m1 = off; off += pp_align(hw);
+    l->m2 = off; off += pp_align(hw);
+    l->total = off;
+}
+extern "C" size_t dl_pp_render_ws_bytes(int H, int W) {
+    PPRLayout l;
+    if (H <= 0 || W <= 0 || (size_t)H * W >= ((size_t)1 << 31)) return 0;
+    ppr_layout(H, W, &l);
+    return l.total;
+}
+
+extern "C" int dl_pp_render_finish(const void *orig, size_t orig_row_stride, const int *owner, const int *rows, int n_cells, void *ws, int H, int W,
+                                   void *overlay, size_t overlay_row_stride, void *refined, size_t refined_row_stride, void *stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (!orig || !owner || !ws || !overlay || !refined || (n_cells > 0 && !rows)) DL_FAIL("dl_pp_render_finish: null argument");
+    if (H <= 0 || W <= 0 || (size_t)H * W >= ((size_t)1 << 31)) DL_FAIL("dl_pp_render_finish: empty problem or too large (H=%d W=%d)", H, W);
+    if (n_cells < 0) DL_FAIL("dl_pp_render_finish: n=%d", n_cells);
+    PPRLayout l;
+    ppr_layout(H, W, &l);
+    char *w = (char *)ws;
+    const int n = H * W, blocks = (n + 255) / 256;
+    int *flag = (int *)(w + l.flag), *label = (int *)(w + l.label);
+    uint8_t *m1 = (uint8_t *)(w + l.m1), *m2 = (uint8_t *)(w + l.m2);
+    if (hipMemsetAsync(flag, 0, (size_t)n * 4, stream) != hipSuccess) DL_FAIL("dl_pp_render_finish: memset");
+    hipLaunchKernelGGL(pp_render_mask_kernel, dim3(blocks), dim3(256), 0, stream, owner, rows, n_cells, H, W, m1, label);
+    hipLaunchKernelGGL(pp_merge_kernel<4>, dim3(blocks), dim3(256), 0, stream, label, H, W);
+    hipLaunchKernelGGL(pp_flatten_kernel, dim3(blocks), dim3(256), 0, stream, label, n);
+    hipLaunchKernelGGL(pp_border_flag_kernel, dim3((2 * (H + W) + 255) / 256), dim3(256), 0, stream, label, H, W, flag);
+    hipLaunchKernelGGL(pp_background_kernel, dim3(blocks), dim3(256), 0, stream, m1, label, flag, n, W);
+    hipLaunchKernelGGL(pp_render_fill_kernel, dim3((H + 3) / 4), dim3(256), 0, stream, m1, H, W);
+    hipLaunchKernelGGL(pp_render_boundary_kernel, dim3(blocks), dim3(256), 0, stream, m1, H, W, m2);
+    hipLaunchKernelGGL(pp_enlarge_kernel, dim3(blocks), dim3(256), 0, stream, m2, H, W, m1);
+    hipLaunchKernelGGL(pp_enlarge_kernel, dim3(blocks), dim3(256), 0, stream, m1, H, W, m2);
+    hipLaunchKernelGGL(pp_final_kernel, dim3(blocks), dim3(256), 0, stream, (const uint8_t *)orig, orig_row_stride, m2, H, W,
+                       (uint8_t *)overlay, overlay_row_stride, (uint8_t *)refined, refined_row_stride);
+    DL_CHECK_LAUNCH("dl_pp_render_finish");
+    return 0;
+}
+
 // ---------------------------------------------------------------------------------------------------- host-only helper
 // calculate_default_size_threshold's kernel density estimate (postprocessing.py:365-447) over the cell list: count bins, bandwidth 1,
 // kde[i] = float32( sum_j exp(-((i*step - v_j)^2 / 2)) / sqrt(2 pi)  / n ), summed over j in list order in float64 -- the reference's

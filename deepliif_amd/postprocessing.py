@@ -12,6 +12,10 @@ the image).  There is no CPU fallback: without the HIP library this module raise
 mapping, every cell's bounding box and simplified outline, as dicts (data versions 3 / 5) or base-92 + Freeman-chain strings (4 / 6).  The outlines are
 traced and encoded on the GPU (dl_pp_outline_count / dl_pp_outline_emit, one lane per cell; outline_cells below); the per-cell Python code the
 reference's functions translate to is kept as route='host', the yardstick.  `offset` places the image inside a slide (wsi.infer_slide_cells).
+
+`cells_to_final_results(data, orig, ...thresholds..., route='gpu', offset=(0, 0), outside='raise')` (:1307-1412) renders such a stored cell list
+back into overlay, refined image and scoring under new thresholds (dl_pp_render_count / _paint / _finish); `pack_cells` uploads a list once for
+repeated calls; route='host' is the numpy restatement the kernels are held to.
 """
 from __future__ import annotations
 
@@ -538,3 +542,373 @@ def compute_cell_results(seg, marker, resolution, version=3, seg_thresh=DEFAULT_
         return cell_results_from_mapping(cm.mask.cpu().numpy(), cm.cells, cm.defaults, version, seg_thresh, noise_thresh, large, offset=offset)
     cells = outline_cells(cm.mask, cm.table, version, offset)
     return {'cells': cells, 'settings': _cell_settings(cm.defaults, version, seg_thresh, noise_thresh, large), 'dataVersion': version}
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# Rendering a STORED cell list (cells_to_final_results, postprocessing.py:1307-1412): overlay, refined image and scoring from the output of
+# compute_cell_results under new thresholds, without a network or the segmentation post-processing.  route 'gpu' = dl_pp_render_count /
+# _paint / _finish; route 'host' = the numpy restatement below (no numba), the yardstick the GPU route is held to.  Both start from the
+# flattened form of the list (PackedCells) and share the per-cell contract of include/deepliif_hip.h: a row {status, class, extent of the
+# vertices, pixels of the full outline} per cell, and "the last counted cell in list order owns an outline pixel".
+# ---------------------------------------------------------------------------------------------------------------
+RENDER_OK, RENDER_MALFORMED, RENDER_BAD_SEGMENT, RENDER_OUTSIDE = 0, 1, 2, 3
+RENDER_STATUS = {RENDER_MALFORMED: 'the stored cell is malformed (no outline point; or its string ends before its header or its numbers, or holds a character outside 35 .. 126)',
+                 RENDER_BAD_SEGMENT: 'two consecutive outline points (or the last and the first) are not joined by one of the eight pixel directions',
+                 RENDER_OUTSIDE: 'an outline point lies outside the image'}
+_MODE_POINTS, _MODE_STRINGS = 0, 1
+_LABEL_UNKNOWN, _LABEL_POSITIVE, _LABEL_NEGATIVE, _LABEL_BACKGROUND, _LABEL_BORDER_POS, _LABEL_BORDER_NEG = 50, 200, 150, 0, 220, 170
+
+
+class PackedCells:
+    """A cell list flattened once (pack_cells): versions 4 / 6 as one byte buffer + int64 offsets, versions 3 / 5 as int32 points + int64
+    offsets + an int32 [n][4] table {size, positive, marker or optical-density value, 0}.  `host` holds the numpy arrays, `dev` the same
+    arrays on `device` (None for a list packed for the host route)."""
+
+    def __init__(self, version, settings, mode, data, offsets, table, device=None):
+        self.version, self.settings, self.mode, self.n = version, dict(settings), mode, int(len(offsets) - 1)
+        self.host = (data, offsets, table)
+        self.device = device
+        self.dev = None
+        if device is not None:
+            up = lambda a: None if a is None else torch.from_numpy(a).to(device)
+            self.dev = (up(data), up(offsets), up(table))
+
+    @property
+    def items(self):
+        return int(self.host[0].shape[0])
+
+
+def pack_cells(data, device=None, upload=True) -> PackedCells:
+    """The dict compute_cell_results returns (or a stored copy of it: {'cells', 'settings', 'dataVersion'}) -> PackedCells on `device`
+    (default: the current CUDA device).  A second cells_to_final_results call on the result costs kernels only.  upload=False keeps the
+    arrays on the host (all that route='host' needs)."""
+    version = data['dataVersion']
+    if version not in (3, 4, 5, 6):
+        raise ValueError(f'unknown cell data version {version!r} (3 .. 6)')
+    cells = data['cells']
+    n = len(cells)
+    offsets = np.zeros(n + 1, dtype=np.int64)
+    table = None
+    if version in (4, 6):
+        try:
+            raw = [c.encode('latin-1') for c in cells]
+        except (UnicodeEncodeError, AttributeError):
+            i = next(j for j, c in enumerate(cells) if not isinstance(c, str) or any(ord(ch) > 255 for ch in c))
+            raise ValueError(f'cell {i} of {n}: not a version-{version} string of characters 35 .. 126') from None
+        np.cumsum([len(r) for r in raw], out=offsets[1:])
+        flat = np.frombuffer(b''.join(raw), dtype=np.uint8).copy()
+        mode = _MODE_STRINGS
+    else:
+        from itertools import chain
+        key = 'od' if version == 5 else 'marker'
+        np.cumsum([len(c['boundary']) for c in cells], out=offsets[1:])
+        pts = np.fromiter(chain.from_iterable(chain.from_iterable(c['boundary'] for c in cells)), dtype=np.int64).reshape(-1, 2)
+        tab = np.zeros((n, 4), dtype=np.int64)
+        if n:
+            tab[:, 0] = [c['size'] for c in cells]
+            tab[:, 1] = [bool(c['positive']) for c in cells]
+            tab[:, 2] = [c.get(key, 0) for c in cells]
+        lim = 2 ** 31 - 1
+        if (len(pts) and (pts.min() < -lim or pts.max() > lim)) or (n and (tab.min() < -lim or tab.max() > lim)):
+            raise ValueError('a coordinate, size or marker value of the cell list does not fit 32 bits')
+        flat, table, mode = np.ascontiguousarray(pts, dtype=np.int32), tab.astype(np.int32), _MODE_POINTS
+    dev = None
+    if upload:
+        dev = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
+    return PackedCells(version, data['settings'], mode, flat, offsets, table, dev)
+
+
+def _render_thresholds(version, settings, size_thresh, marker_thresh, size_thresh_upper, od_thresh_lower, od_thresh_upper):
+    """:1346-1361 -> (the thresholds as the scoring reports them, the same as dl_pp_render_thresh: integer bounds that decide like the given
+    numbers do on integer sizes and values -- x > t iff x > floor(t), x < t iff x < ceil(t))"""
+    if version in (3, 4):
+        od_thresh_lower = od_thresh_upper = None
+    else:
+        marker_thresh = None
+    if size_thresh is None:
+        size_thresh = 0
+    elif isinstance(size_thresh, str) and size_thresh == 'default':
+        size_thresh = settings['default_size_thresh']
+    if isinstance(marker_thresh, str) and marker_thresh == 'default':
+        marker_thresh = settings['default_marker_thresh']
+    big = 1 << 62
+
+    def bound(v, up):
+        if v is None:
+            return 0, 0
+        if v != v:
+            raise ValueError('a threshold is not a number')
+        v = max(-big, min(big, v))
+        return int(math.ceil(v) if up else math.floor(v)), 1
+
+    th = L.RenderThresh()
+    th.size_lower = bound(size_thresh, False)[0]
+    th.size_upper, th.has_size_upper = bound(size_thresh_upper, True)
+    th.marker, th.has_marker = bound(marker_thresh, False)
+    th.od_lower, th.has_od_lower = bound(od_thresh_lower, True)
+    th.od_upper, th.has_od_upper = bound(od_thresh_upper, False)
+    return {'size_thresh': size_thresh, 'size_thresh_upper': size_thresh_upper, 'marker_thresh': marker_thresh}, th
+
+
+def _render_class(size, positive, value, th, v6) -> int:
+    """:1371-1380 -> 0 not counted / 1 positive / 2 negative"""
+    if not (size > th.size_lower and (not th.has_size_upper or size < th.size_upper)):
+        return 0
+    pos = bool(positive)
+    if not v6 and th.has_marker and value > th.marker:
+        pos = True
+    if v6:
+        if th.has_od_lower and value < th.od_lower:
+            pos = False
+        elif th.has_od_upper and value > th.od_upper:
+            pos = False
+    return 1 if pos else 2
+
+
+def _render_vertices(packed, i):
+    """cell i of a host-side PackedCells -> (size, positive, value, [(x, y), ...]); None when not even the numbers can be read, and no
+    point list when only the chain is malformed.  Strings are decoded like decode_cell_data_v4 does, with every byte checked; every chain
+    character is one vertex (a repeated direction changes no pixel)."""
+    data, offsets, table = packed.host
+    b, e = int(offsets[i]), int(offsets[i + 1])
+    if b < 0 or e <= b or e > len(data):
+        return None
+    if packed.mode == _MODE_POINTS:
+        return int(table[i, 0]), int(table[i, 1]), int(table[i, 2]), [(int(x), int(y)) for x, y in data[b:e].tolist()]
+    s = data[b:e].tolist()
+    bad = lambda part: any(c < 35 or c > 126 for c in part)
+    if bad(s[:1]):
+        return None
+    n = s[0] - 35
+    w_size, w_tl, w_off = n // 16 + 1, (n // 4) % 4 + 1, n % 4 + 1
+    head = 1 + w_size + 2 + 2 * w_tl + 6 * w_off
+    if len(s) < head or bad(s[:head]):
+        return None
+    pos = 1
+    nums = []
+    for w in (w_size, 2, w_tl, w_tl) + (w_off,) * 6:
+        v = 0
+        for c in s[pos:pos + w]:
+            v = v * 92 + (c - 35)
+        nums.append(v)
+        pos += w
+    size, cls, ax, ay = nums[:4]
+    if bad(s[head:]):
+        return size, cls % 2, cls // 2, None
+    x, y = ax + nums[8], ay + nums[9]
+    pts = [(x, y)]
+    for c in s[head:]:
+        steps, code = divmod(c - 35, 8)
+        dx, dy = _FREEMAN_STEP[code]
+        x, y = x + dx * steps, y + dy * steps
+        pts.append((x, y))
+    return size, cls % 2, cls // 2, pts
+
+
+def render_rows_host(packed, th, offset, H, W, paint=True):
+    """The host statement of dl_pp_render_count (+ _paint): -> (rows int32 [n][8], owner int32 [H][W] or None).  Sequential, in list order:
+    a later cell overwrites an earlier one (= the maximum index the kernel keeps)."""
+    v6 = packed.version in (5, 6)
+    ox, oy = int(offset[0]), int(offset[1])
+    sat = lambda v: max(-2 ** 31, min(2 ** 31 - 1, v))
+    rows = np.zeros((packed.n, 8), dtype=np.int32)
+    outlines = []
+    for i in range(packed.n):
+        c = _render_vertices(packed, i)
+        rows[i, 0] = RENDER_MALFORMED
+        if c is None:
+            outlines.append(None)
+            continue
+        size, positive, value, pts = c
+        rows[i, 1] = _render_class(size, positive, value, th, v6)
+        if pts is None:
+            outlines.append(None)
+            continue
+        pts = [(x - ox, y - oy) for x, y in pts]
+        bad, pixels = False, 1
+        for (ax, ay), (bx, by) in zip(pts, pts[1:] + pts[:1]):
+            dx, dy = abs(bx - ax), abs(by - ay)
+            bad |= dx != 0 and dy != 0 and dx != dy
+            pixels += max(dx, dy)
+        dx, dy = abs(pts[0][0] - pts[-1][0]), abs(pts[0][1] - pts[-1][1])
+        pixels -= min(max(dx, dy), 1)                                  # the closing run stops in front of the first point
+        xs, ys = [p[0] for p in pts], [p[1] for p in pts]
+        rows[i, 2:7] = [sat(min(xs)), sat(min(ys)), sat(max(xs)), sat(max(ys)), sat(pixels)]
+        rows[i, 0] = RENDER_BAD_SEGMENT if bad else (RENDER_OUTSIDE if min(xs) < 0 or min(ys) < 0 or max(xs) >= W or max(ys) >= H else RENDER_OK)
+        outlines.append(pts if rows[i, 0] == RENDER_OK and rows[i, 1] != 0 else None)
+    if not paint:
+        return rows, None
+    owner = np.full((H, W), -1, dtype=np.int32)
+    sgn = lambda v: (v > 0) - (v < 0)
+    for i, pts in enumerate(outlines):
+        if pts is None:
+            continue
+        full = [pts[0]]                                                # make_full_contour (:637-682)
+        for p in pts[1:] + pts[:1]:
+            x, y = full[-1]
+            dx, dy = sgn(p[0] - x), sgn(p[1] - y)
+            for _ in range(max(abs(p[0] - x), abs(p[1] - y))):
+                x, y = x + dx, y + dy
+                full.append((x, y))
+        if len(full) > 1 and full[-1] == full[0]:
+            full.pop()
+        a = np.asarray(full, dtype=np.int64)
+        owner[a[:, 1], a[:, 0]] = i
+    return rows, owner
+
+
+def render_mask_host(owner, rows):
+    """owner map + classes -> the final label mask: mark_background (:194-232), fill_cells (:1075-1099), create_outer_boundary (:1103-1122),
+    enlarge_cell_boundaries (:1003-1030) twice, as whole-array numpy statements of the five order-free rules"""
+    H, W = owner.shape
+    cls = np.concatenate([rows[:, 1].astype(np.int64), [0]])          # owner -1 -> the appended 0
+    oc = cls[owner]
+    mask = np.where(owner < 0, _LABEL_UNKNOWN, np.where(oc == 1, _LABEL_BORDER_POS, _LABEL_BORDER_NEG)).astype(np.uint8)
+    # background: flood fill of the UNKNOWN pixels from the image border, 4-connected (a frame of a non-UNKNOWN value stops the walk)
+    pad = np.full((H + 2, W + 2), 255, dtype=np.uint8)
+    pad[1:-1, 1:-1] = mask
+    flat = bytearray(pad.tobytes())
+    S = W + 2
+    border = np.zeros((H, W), dtype=bool)
+    border[0, :] = border[-1, :] = border[:, 0] = border[:, -1] = True
+    ys, xs = np.nonzero(border & (mask == _LABEL_UNKNOWN))
+    stack = ((ys + 1) * S + xs + 1).tolist()
+    for p in stack:
+        flat[p] = _LABEL_BACKGROUND
+    while stack:
+        p = stack.pop()
+        for q in (p - S, p - 1, p + 1, p + S):
+            if flat[q] == _LABEL_UNKNOWN:
+                flat[q] = _LABEL_BACKGROUND
+                stack.append(q)
+    mask = np.frombuffer(bytes(flat), dtype=np.uint8).reshape(H + 2, S)[1:-1, 1:-1].copy()
+    # fill: an UNKNOWN pixel takes the class of the nearest pixel to its left that is not UNKNOWN
+    known = mask != _LABEL_UNKNOWN
+    src = np.maximum.accumulate(np.where(known, np.arange(W)[None, :], -1), axis=1)
+    left = np.take_along_axis(mask, np.maximum(src, 0), axis=1)
+    fill = np.where((src >= 0) & (left == _LABEL_BORDER_POS), _LABEL_POSITIVE, _LABEL_NEGATIVE).astype(np.uint8)
+    mask = np.where(known, mask, fill)
+    mask[mask == _LABEL_BORDER_POS] = _LABEL_POSITIVE
+    mask[mask == _LABEL_BORDER_NEG] = _LABEL_NEGATIVE
+
+    def shifted(m, dy, dx):
+        """m[y + dy, x + dx], 0 outside"""
+        out = np.zeros_like(m)
+        out[max(-dy, 0):H - max(dy, 0), max(-dx, 0):W - max(dx, 0)] = m[max(dy, 0):H + min(dy, 0), max(dx, 0):W + min(dx, 0)]
+        return out
+
+    # outer boundary: the first POSITIVE / NEGATIVE neighbour among up, left, right, down
+    out = mask.copy()
+    todo = mask == _LABEL_BACKGROUND
+    for dy, dx in ((-1, 0), (0, -1), (0, 1), (1, 0)):
+        nb = shifted(mask, dy, dx)
+        for lab, border_lab in ((_LABEL_POSITIVE, _LABEL_BORDER_POS), (_LABEL_NEGATIVE, _LABEL_BORDER_NEG)):
+            hit = todo & (nb == lab)
+            out[hit] = border_lab
+            todo &= ~hit
+    mask = out
+    for _ in range(2):                                                 # enlarge: the first border neighbour of the 8, in raster order
+        out = mask.copy()
+        todo = mask == _LABEL_BACKGROUND
+        for dy in (-1, 0, 1):
+            for dx in (-1, 0, 1):
+                if dy == 0 and dx == 0:
+                    continue
+                nb = shifted(mask, dy, dx)
+                hit = todo & ((nb == _LABEL_BORDER_POS) | (nb == _LABEL_BORDER_NEG))
+                out[hit] = nb[hit]
+                todo &= ~hit
+        mask = out
+    return mask
+
+
+def _final_images_host(orig, mask):
+    """create_final_images (:1033-1071)"""
+    overlay, refined = orig.copy(), np.zeros_like(orig)
+    overlay[mask == _LABEL_BORDER_POS] = (255, 0, 0)
+    overlay[mask == _LABEL_BORDER_NEG] = (0, 0, 255)
+    refined[..., 1][(mask == _LABEL_BORDER_POS) | (mask == _LABEL_BORDER_NEG)] = 255
+    refined[..., 0][mask == _LABEL_POSITIVE] = 255
+    refined[..., 2][mask == _LABEL_NEGATIVE] = 255
+    return overlay, refined
+
+
+def _render_refusals(rows, n, outside):
+    """raises for the first cell the count pass refused: a malformed cell always (the reference decodes every cell), a bad segment or
+    (outside='raise') a vertex outside the image only for a COUNTED cell (the reference never rasterises the others)"""
+    st, cl = rows[:, 0], rows[:, 1]
+    bad = (st == RENDER_MALFORMED) | ((cl != 0) & ((st == RENDER_BAD_SEGMENT) | ((st == RENDER_OUTSIDE) & (outside == 'raise'))))
+    if bad.any():
+        i = int(np.flatnonzero(bad)[0])
+        hint = "; outside='skip' leaves such cells out" if st[i] == RENDER_OUTSIDE else ''
+        raise ValueError(f'cells_to_final_results: cell {i} of {n}: {RENDER_STATUS[int(st[i])]} (vertices span x {int(rows[i, 2])} .. {int(rows[i, 4])}, '
+                         f'y {int(rows[i, 3])} .. {int(rows[i, 5])}){hint}')
+
+
+def cells_to_final_results(data, orig, size_thresh='default', marker_thresh=None, size_thresh_upper=None, od_thresh_lower=None, od_thresh_upper=None,
+                           *, route='gpu', offset=(0, 0), outside='raise', return_tensors: bool = False, device=None):
+    """deepliif/postprocessing.py:1307-1412 -> (overlay, refined, scoring) from stored cell data.  data: the dict of compute_cell_results (any
+    data version) or a PackedCells; orig: PIL image, uint8 ndarray or uint8 CUDA tensor (H x W x 3).  Versions 3 / 4 ignore the optical-density
+    thresholds, 5 / 6 the marker threshold.
+    route: 'gpu' (dl_pp_render_*) or 'host' (numpy, the yardstick).  offset: subtracted from every coordinate (slide-level lists);
+    outside: 'raise' = ValueError for the first counted cell with an outline point outside the image, 'skip' = such cells are neither painted
+    nor counted.  return_tensors / device as compute_final_results."""
+    if route not in ('gpu', 'host'):
+        raise ValueError(f"unknown route {route!r} ('gpu' | 'host')")
+    if outside not in ('raise', 'skip'):
+        raise ValueError(f"unknown outside {outside!r} ('raise' | 'skip')")
+    ox, oy = int(offset[0]), int(offset[1])
+    if isinstance(data, PackedCells):
+        packed = data
+    else:
+        packed = pack_cells(data, device, upload=(route == 'gpu'))
+    shown, th = _render_thresholds(packed.version, packed.settings, size_thresh, marker_thresh, size_thresh_upper, od_thresh_lower, od_thresh_upper)
+    n = packed.n
+    if route == 'host':
+        if isinstance(orig, torch.Tensor):
+            orig_np = orig.cpu().numpy()
+        else:
+            orig_np = _to_u8_cuda(orig, 'cpu').numpy()
+        H, W = orig_np.shape[:2]
+        rows, owner = render_rows_host(packed, th, (ox, oy), H, W)          # (paints the cells it found in order only)
+        _render_refusals(rows, n, outside)
+        overlay, refined = _final_images_host(orig_np, render_mask_host(owner, rows))
+        if return_tensors:
+            overlay, refined = torch.from_numpy(overlay), torch.from_numpy(refined)
+    else:
+        lib = ops.impl().lib
+        dev = torch.device(device) if device is not None else (packed.device or (orig.device if isinstance(orig, torch.Tensor) and orig.is_cuda
+                                                                                   else torch.device('cuda', torch.cuda.current_device())))
+        if packed.dev is None or packed.device != dev:
+            packed = PackedCells(packed.version, packed.settings, packed.mode, *packed.host, device=dev)
+        orig_t = _to_u8_cuda(orig, dev)
+        H, W = int(orig_t.shape[0]), int(orig_t.shape[1])
+        ops._need_cuda(orig_t)
+        nbytes = int(lib.dl_pp_render_ws_bytes(H, W))
+        if nbytes == 0:
+            raise RuntimeError('dl_pp_render_ws_bytes failed (empty or too large image)')
+        data_d, offsets_d, table_d = packed.dev
+        p, stream = ops._ptr, ops._stream(orig_t)
+        rows_d = torch.empty((max(n, 1), 8), dtype=torch.int32, device=dev)
+        L.check(lib.dl_pp_render_count(packed.mode, 1 if packed.version in (5, 6) else 0, p(data_d), packed.items, p(offsets_d), p(table_d), n,
+                                       C.byref(th), ox, oy, H, W, p(rows_d), stream), 'dl_pp_render_count', lib)
+        rows = rows_d[:n].cpu().numpy()
+        _render_refusals(rows, n, outside)
+        owner = torch.empty((H, W), dtype=torch.int32, device=dev)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        overlay = torch.empty((H, W, 3), dtype=torch.uint8, device=dev)
+        refined = torch.empty((H, W, 3), dtype=torch.uint8, device=dev)
+        L.check(lib.dl_pp_render_paint(packed.mode, p(data_d), packed.items, p(offsets_d), n, p(rows_d), ox, oy, H, W, p(owner), stream),
+                'dl_pp_render_paint', lib)
+        L.check(lib.dl_pp_render_finish(p(orig_t), orig_t.stride(0), p(owner), p(rows_d), n, p(ws), H, W, p(overlay), overlay.stride(0),
+                                        p(refined), refined.stride(0), stream), 'dl_pp_render_finish', lib)
+        if not return_tensors:
+            overlay, refined = overlay.cpu().numpy(), refined.cpu().numpy()
+    counted = rows[:, 0] == RENDER_OK
+    num_pos, num_neg = int((counted & (rows[:, 1] == 1)).sum()), int((counted & (rows[:, 1] == 2)).sum())
+    num_total = num_pos + num_neg
+    scoring = {'num_total': num_total, 'num_pos': num_pos, 'num_neg': num_neg,
+               'percent_pos': round(num_pos / num_total * 100, 1) if num_pos > 0 else 0,
+               'seg_thresh': packed.settings['seg_thresh'], 'size_thresh': shown['size_thresh'], 'size_thresh_upper': shown['size_thresh_upper'],
+               'marker_thresh': shown['marker_thresh']}
+    return overlay, refined, scoring

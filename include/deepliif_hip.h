@@ -624,6 +624,47 @@ int dl_pp_outline_count(const void *mask, int H, int W, const int *cells, int n,
 int dl_pp_outline_emit(const void *mask, int H, int W, const int *cells, int *counts, const long long *offsets, int n, int ox, int oy,
                        int mode, void *out, long long out_items, void *stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * Rendering a stored cell list (deepliif/postprocessing.py: cells_to_final_results :1307-1412 = the classification of :1371-1380 +
+ * make_full_contour :637-682 painted into a label map + mark_background :194-232 + fill_cells :1075-1099 + create_outer_boundary
+ * :1103-1122 + enlarge_cell_boundaries twice + create_final_images).  Bit-exact with the reference; all integer work.
+ *   mode DL_PP_OUTLINE_STRINGS: data = the cells' encode_cell_data_v4 strings back to back (bytes), offsets int64 [n + 1] in bytes,
+ *        table unused (NULL); the two classification digits carry value * 2 + positive;
+ *   mode DL_PP_OUTLINE_POINTS:  data = int32 [data_items][2], every cell's simplified outline vertices (x, y) back to back, offsets
+ *        int64 [n + 1] in vertices, table int32 [n][4] = {size, positive, marker or optical-density value, 0};
+ *   v6 != 0: `value` is an optical density (data versions 5 / 6: the marker threshold is ignored), else a marker value (versions 3 / 4:
+ *        the optical-density thresholds are ignored);
+ *   (ox, oy) is SUBTRACTED from every coordinate before it is used (a slide-level list rendered into one region);
+ *   rows   int32 [n][8] (device): {status, class (0 = not counted, 1 = positive, 2 = negative), min x, min y, max x, max y of the
+ *        vertices (saturated to int32), pixels of the full outline, 0}.  Status, the first that applies:
+ *        _MALFORMED   the cell's range is empty or not inside [0, data_items); the string ends before its header or its numbers, or holds
+ *                     a byte outside 35 .. 126 (class 0 when the numbers could not be read);
+ *        _BAD_SEGMENT a vector between consecutive vertices, or the closing one, is not a multiple of one of the eight directions
+ *                     (make_full_contour would not terminate);
+ *        _OUTSIDE     a vertex lies outside the image after the offset.
+ * dl_pp_render_count: one lane per cell, O(vertices), reads nothing outside [offsets[i], offsets[i + 1]).
+ * dl_pp_render_paint: sets owner (int32 [H][W]) to -1, then every cell with status OK and class != 0 walks the pixels of
+ *        make_full_contour and stores owner[pixel] = max(owner[pixel], i): the reference's "the later cell overwrites".
+ * dl_pp_render_finish: owner + rows -> overlay and refined images; ws = dl_pp_render_ws_bytes(H, W) bytes (about 10 per pixel; 0 = empty
+ *        or too large image).  n = 0 (rows may be NULL, owner all
+ *        -1) gives overlay = orig and refined = 0.
+ * ---------------------------------------------------------------------------------------------------------- */
+#define DL_PP_RENDER_OK 0
+#define DL_PP_RENDER_MALFORMED 1
+#define DL_PP_RENDER_BAD_SEGMENT 2
+#define DL_PP_RENDER_OUTSIDE 3
+typedef struct dl_pp_render_thresh {      /* counted: size > size_lower and (no upper bound or size < size_upper); :1371-1380 */
+    long long size_lower, size_upper, marker, od_lower, od_upper;
+    int has_size_upper, has_marker, has_od_lower, has_od_upper;
+} dl_pp_render_thresh;
+int dl_pp_render_count(int mode, int v6, const void *data, long long data_items, const long long *offsets, const int *table, int n,
+                       const dl_pp_render_thresh *thresh, int ox, int oy, int H, int W, int *rows, void *stream);
+int dl_pp_render_paint(int mode, const void *data, long long data_items, const long long *offsets, int n, const int *rows, int ox, int oy,
+                       int H, int W, int *owner, void *stream);
+size_t dl_pp_render_ws_bytes(int H, int W);
+int dl_pp_render_finish(const void *orig, size_t orig_row_stride, const int *owner, const int *rows, int n, void *ws, int H, int W,
+                        void *overlay, size_t overlay_row_stride, void *refined, size_t refined_row_stride, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
