@@ -21,6 +21,7 @@ NORM_INSTANCE, NORM_BATCH = 0, 1
 LOSS_BCE_LOGITS, LOSS_MSE, LOSS_SMOOTH_L1, LOSS_L1, LOSS_LINEAR = 0, 1, 2, 3, 4
 MAX_TAPS, MAX_PHASES = 64, 4
 WGRAD_MULTI_MAX = 24
+WGRAD_C4_PARTS = 512        # DL_WGRAD_C4_PARTS: the split-K of the persistent 7x7 stem / head weight gradient (dl_wgrad_route.fixed_splitk)
 DL_VERSION = 118
 
 i32 = C.c_int32
@@ -54,6 +55,10 @@ class WgradReduceEntry(C.Structure):
     _fields_ = [('slab', C.c_void_p), ('grad', C.c_void_p),
                 ('splitk', i32), ('CAp', i32), ('CBp', i32), ('J', i32), ('CA', i32), ('CB', i32), ('KK', i32), ('accumulate', i32), ('stack_kw', i32),
                 ('block0', i32), ('nblocks', i32), ('kstride', i32)]
+
+
+class WgradRoute(C.Structure):         # dl_wgrad_route
+    _fields_ = [('name', C.c_char_p), ('tiles', i32), ('ksteps', i32), ('batched', i32), ('deferrable', i32), ('takes_split', i32), ('fixed_splitk', i32)]
 
 
 class PackDesc(C.Structure):
@@ -113,6 +118,7 @@ SIGNATURES = {
     'dl_conv_wgrad_slabs': (_i, [C.POINTER(WgradDesc), _vp, _vp, _vp, _vp, C.POINTER(WgradReduceEntry), _vp]),
     'dl_wgrad_reduce_batch': (_i, [_vp, _i, _i, _vp]),
     'dl_wgrad_plan': (_i, [C.POINTER(WgradDesc), C.POINTER(i32), C.POINTER(i32), C.POINTER(C.c_char_p)]),
+    'dl_wgrad_route_info': (_i, [C.POINTER(WgradDesc), C.POINTER(WgradRoute)]),
     'dl_conv_wgrad_multi': (_i, [C.POINTER(WgradDesc), _i, _vp, _vp, _vp, _vp, C.POINTER(WgradReduceEntry), _vp]),
     'dl_pack_weights': (_i, [C.POINTER(PackDesc), _vp, _vp, _vp, _vp]),
     'dl_pack_job_bytes': (C.c_size_t, []),
@@ -207,6 +213,14 @@ def load(half: str = 'bf16'):
         raise HipLibraryError(f'{os.path.basename(path)} version {lib.dl_version()} != {DL_VERSION} (stale build)')
     if lib.dl_half_format() != (HALF_BF16 if half == 'bf16' else HALF_FP16):
         raise HipLibraryError(f'{path} was built for the other 16-bit format (dl_half_format() = {lib.dl_half_format()})')
+    # answers of dl_wgrad_route_info by descriptor bytes (ops.HipBackend.wgrad_route): they depend on the switches, so reading those again empties the memo
+    lib.wgrad_route_memo = {}
+    c_reload = lib.dl_switches_reload
+
+    def reload():
+        c_reload()
+        lib.wgrad_route_memo.clear()
+    lib.dl_switches_reload = reload
     _libs[half] = lib
     return lib
 

@@ -42,6 +42,23 @@ struct WgradLayers {
     float *slab[WGRAD_MULTI_MAX];
 };
 
+// ---- what the launchers below share (host)
+// the split-K pixel range of the kernels that stage `bp` pixels per K step (a multiple of bp), and bp pixels as a mixed-radix step over (Hp*Wp, Wp, 1)
+static void wgrad_pixel_steps(WgradArgs &a, int bp) {
+    a.pchunk = ((a.Ptot + a.splitk - 1) / a.splitk + bp - 1) / bp * bp;
+    const int hw = a.Hp * a.Wp;
+    a.dn = bp / hw; a.dh = (bp % hw) / a.Wp; a.dw = (bp % hw) % a.Wp;
+}
+
+// raises a kernel's dynamic-LDS limit, once (`done`: the launcher's own static flag, one per kernel instance)
+static int wgrad_lds_limit(const void *kern, size_t smem, bool *done, const char *who) {
+    if (*done) return 0;
+    const hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+    if (e != hipSuccess) DL_FAIL("%s: hipFuncSetAttribute(%zu): %s", who, smem, hipGetErrorString(e));
+    *done = true;
+    return 0;
+}
+
 template <typename T> struct RawW;
 template <> struct RawW<bf16_t> { u32x4_t v; };
 template <> struct RawW<float> { f32x4_t a, b; };
@@ -683,15 +700,9 @@ static int launch_wgrad_8ph(WgradArgs a, hipStream_t stream) {
     constexpr size_t smem = (size_t)2 * 64 * (256 + 256) * sizeof(bf16_t);
     a.tiles_a = a.CAp / 256;
     a.tiles_j = (a.J + 255) / 256;
-    a.pchunk = ((a.Ptot + a.splitk - 1) / a.splitk + 63) / 64 * 64;
-    const int hw = a.Hp * a.Wp;
-    a.dn = 64 / hw; a.dh = (64 % hw) / a.Wp; a.dw = (64 % hw) % a.Wp;
+    wgrad_pixel_steps(a, 64);
     static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(wgrad_8ph_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-        if (e != hipSuccess) DL_FAIL("dl_conv_wgrad: hipFuncSetAttribute: %s", hipGetErrorString(e));
-        attr_set = true;
-    }
+    if (wgrad_lds_limit(reinterpret_cast<const void *>(wgrad_8ph_kernel), smem, &attr_set, "dl_conv_wgrad(8-phase)")) return -1;
     hipLaunchKernelGGL(wgrad_8ph_kernel, dim3(a.tiles_a * a.tiles_j, a.splitk), dim3(512), smem, stream, a);
     DL_CHECK_LAUNCH("dl_conv_wgrad(8-phase)");
     return 0;
@@ -702,16 +713,10 @@ static int launch_wgrad_glds_v(WgradArgs a, const WgradLayers &lay, int n, hipSt
     constexpr size_t smem = (size_t)2 * 64 * (BA + 256) * sizeof(bf16_t);
     a.tiles_a = a.CAp / BA;
     a.tiles_j = (a.J + 255) / 256;
-    a.pchunk = ((a.Ptot + a.splitk - 1) / a.splitk + 63) / 64 * 64;
-    const int hw = a.Hp * a.Wp;
-    a.dn = 64 / hw; a.dh = (64 % hw) / a.Wp; a.dw = (64 % hw) % a.Wp;
+    wgrad_pixel_steps(a, 64);
     auto kern = wgrad_glds_kernel<BA, WA, WJ, TRASM>;
     static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-        if (e != hipSuccess) DL_FAIL("dl_conv_wgrad: hipFuncSetAttribute: %s", hipGetErrorString(e));
-        attr_set = true;
-    }
+    if (wgrad_lds_limit(reinterpret_cast<const void *>(kern), smem, &attr_set, "dl_conv_wgrad(glds)")) return -1;
     hipLaunchKernelGGL(kern, dim3(a.tiles_a * a.tiles_j, a.splitk, n), dim3(512), smem, stream, a, lay);
     DL_CHECK_LAUNCH("dl_conv_wgrad(glds)");
     return 0;
@@ -841,22 +846,10 @@ static int launch_wgrad(WgradArgs a, hipStream_t stream) {
     a.tiles_j = (a.J + 127) / 128;
     auto kern = wgrad_kernel<T, PREC, BA, WA, WJ>;
     static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-        if (e != hipSuccess) DL_FAIL("dl_conv_wgrad: hipFuncSetAttribute: %s", hipGetErrorString(e));
-        attr_set = true;
-    }
+    if (wgrad_lds_limit(reinterpret_cast<const void *>(kern), smem, &attr_set, "dl_conv_wgrad")) return -1;
     hipLaunchKernelGGL(kern, dim3(a.tiles_a * a.tiles_j, a.splitk), dim3(256), smem, stream, a);
     DL_CHECK_LAUNCH("dl_conv_wgrad");
     return 0;
-}
-
-template <typename T, int PREC>
-static int dispatch_wgrad(const WgradArgs &a, hipStream_t stream) {
-    if (a.CAp <= 16) return launch_wgrad<T, PREC, 16, 1, 4>(a, stream);
-    if (a.CAp <= 32) return launch_wgrad<T, PREC, 32, 1, 4>(a, stream);
-    if (a.CAp <= 64) return launch_wgrad<T, PREC, 64, 2, 2>(a, stream);
-    return launch_wgrad<T, PREC, 128, 2, 2>(a, stream);
 }
 
 #include "wgrad_c4.h"
@@ -878,54 +871,137 @@ extern "C" size_t dl_wgrad_slab_floats(const dl_wgrad_desc *d) {
     return (size_t)d->splitk * ((size_t)d->CAp * d->KH * d->KW * d->CBp + wgrad_slab_pad());
 }
 
-// Which kernel of the general path serves a descriptor (one decision for dl_conv_wgrad, dl_conv_wgrad_multi and dl_wgrad_plan)
-enum WgradKernel { WK_GENERIC = 0, WK_GLDS256, WK_GLDS128, WK_X3_256, WK_X3_128, WK_8PH, WK_4PH_X3, WK_4PH_X3_NOPRIO, WK_W4 };
+// ------------------------------------------------------------------------------------------------------------------
+// Routing.  wgrad_route() is the ONE place that chooses among the weight-gradient kernels; dl_conv_wgrad, dl_conv_wgrad_slabs, dl_conv_wgrad_multi launch what
+// it says and dl_wgrad_plan, dl_conv_wgrad_deferrable, dl_wgrad_route_info report it (tests/test_wgrad_routing_host.py holds its answers to a snapshot).
+// ------------------------------------------------------------------------------------------------------------------
+enum WgradRoute { WR_GENERIC = 0, WR_GLDS256, WR_GLDS128, WR_X3_256, WR_X3_128, WR_W4, WR_C4, WR_C4_X3, WR_COUNT };
 
-static int wgrad_kernel_of(const dl_wgrad_desc *d, int *err) {
-    *err = 0;
+// What is fixed per route: the name dl_wgrad_plan reports, the output tile (rows of CAp x columns of J = KH*KW*CBp), the pixels of one K step, whether
+// dl_conv_wgrad_multi can batch it, and whether the kernel reduces its partials into the gradient itself (no slabs left for a deferred reduction).
+struct WgradRouteRow { const char *name; int rows, cols, kpix; bool batched, in_place; };
+static const WgradRouteRow g_wgrad_routes[] = {
+    {"wgrad_kernel", 0, 128, 32, false, false},                 // rows: wgrad_generic_rows(CAp)
+    {"wgrad_glds_kernel<256>", 256, 256, 64, true, false},
+    {"wgrad_glds_kernel<128>", 128, 256, 64, true, false},
+    {"wgrad_glds_x3_kernel<256>", 256, 256, 32, true, false},
+    {"wgrad_glds_x3_kernel<128>", 128, 256, 32, true, false},
+    {"wgrad_w4_kernel", 128, 3 * 128, 128, true, false},        // 128 x 128 channels x one kernel row (3 taps); a K step is one image row of 128 pixels
+    {"wgrad_c4", 0, 0, 0, false, true},                         // persistent: DL_WGRAD_C4_PARTS workgroups share the image tiles among themselves
+    {"wgrad_c4", 0, 0, 0, false, true},                         // (the strict form of the same kernel, wgrad_x3.h)
+};
+static_assert(sizeof(g_wgrad_routes) / sizeof(g_wgrad_routes[0]) == WR_COUNT, "one row per WgradRoute");
+
+static int wgrad_generic_rows(int CAp) { return CAp <= 16 ? 16 : (CAp <= 32 ? 32 : (CAp <= 64 ? 64 : 128)); }
+
+struct WgradRouted {
+    int route;          // WgradRoute
+    int variant;        // dev build only, a leaf of the 256-row direct-to-LDS arms: 1 = the phased schedule (wgrad_8ph_kernel / wgrad_4ph_x3_kernel), 2 = 4-phase x3 without s_setprio
+    int c4_form;        // 7x7 stem / head shape, whatever d->splitk says: 0 no, 1 P wide / Q small (stem), 2 P small / Q wide (head)
+    int tiles, ksteps;  // output tiles per layer; K steps of one tile at split-K 1 (0 / 0: the kernel partitions its own work)
+    bool batched;       // dl_conv_wgrad_multi takes it
+    bool takes_split;   // a strict direct-to-LDS kernel serves the shape: operands without a staged activation may be split copies
+    bool split_error;   // p_split / q_split on a descriptor whose kernel cannot read them
+};
+
+static WgradRouted wgrad_route(const dl_wgrad_desc *d) {
+    WgradRouted r;
+    memset(&r, 0, sizeof(r));
     const int J = d->KH * d->KW * d->CBp;
     const long Ptot = (long)d->N * d->Hp * d->Wp;
+    const bool bf16 = d->dtype == DL_BF16 && d->prec == DL_PREC_BF16, strict = d->dtype == DL_F32 && d->prec == DL_PREC_BF16X3;
+    const bool no_act = d->p_act == DL_ACT_NONE && d->q_act == DL_ACT_NONE, any_split = d->p_split || d->q_split;
+
+    // ---- the 7x7 stem / head (wgrad_c4.h; strict: wgrad_x3.h): one 64-channel and one <= 4-channel operand, whole 4 x 64 pixel tiles.  DL_NO_WGRAD_C4=1
+    // switches both off, DL_NO_C4_X3 the strict one.  The kernels partition the image themselves: they run only with splitk == DL_WGRAD_C4_PARTS.
+    const bool c4_on = !dl_switch_is_one(DL_SW_NO_WGRAD_C4) && (bf16 || (strict && !any_split && dl_switch(DL_SW_NO_C4_X3) == nullptr));
+    if (c4_on && no_act && d->KH == 7 && d->KW == 7 && d->step == 1 && d->pad == 3 && (d->pad_w < 0 || d->pad_w == 3) && d->pad_mode == DL_PAD_ZERO &&
+        !d->stack_kw && d->Hp == d->Hq && d->Wp == d->Wq && d->Hp % 4 == 0 && d->Wp % 64 == 0) {
+        if (d->CAp == 64 && d->CA <= 64 && d->CBp == 8 && d->CB <= 4) r.c4_form = 1;
+        else if (d->CAp == 8 && d->CA <= 4 && d->CBp == 64 && d->CB <= 64) r.c4_form = 2;
+    }
+    if (r.c4_form && d->splitk == DL_WGRAD_C4_PARTS) {
+        r.route = bf16 ? WR_C4 : WR_C4_X3;
+        return r;
+    }
+
+    // ---- the direct-to-LDS kernels: bf16 policy without a staged activation; strict policy (wgrad_x3.h: relu / lrelu are applied while the tile is split)
     static const bool no_glds = DL_DEV_ENV("DL_NO_GLDS") != nullptr;
-    const bool fast = d->dtype == DL_BF16 && d->prec == DL_PREC_BF16 && d->p_act == DL_ACT_NONE && d->q_act == DL_ACT_NONE &&
-                      d->pad_mode == DL_PAD_ZERO && J >= 256 && Ptot >= 64L * d->splitk && !no_glds;
-    // "1": the four-phase schedule (wgrad_8ph_kernel).  OFF by default -- measured r02, same box, ResnetBlock shape, kernel + reduce:
-    // 217-225 us vs 191-193 us for the one-barrier kernel in all three variants tried (reads retired before the first barrier; restage
-    // two phases later without forced waits; address arithmetic moved into the MFMA shadow).  The one-barrier kernel alone is 172 us,
-    // within 8 % of the forward's 8-phase kernel (155-160 us), so there was little left to win here.
-    static const char *w8 = DL_DEV_ENV("DL_WGRAD_8PH");
-    // strict policy on the direct-to-LDS path (wgrad_x3.h); DL_NO_X3_GLDS=1: the round-1 register-staged kernel (A/B)
-    const bool no_x3 = dl_switch(DL_SW_NO_X3_GLDS) != nullptr;
+    const bool fast = bf16 && no_act && d->pad_mode == DL_PAD_ZERO && J >= 256 && Ptot >= 64L * d->splitk && !no_glds;
+    // DL_NO_X3_GLDS=1: the strict policy on the round-1 register-staged kernel (A/B)
     const bool act_ok3 = (d->p_act == DL_ACT_NONE || d->p_act == DL_ACT_RELU || d->p_act == DL_ACT_LRELU) &&
                          (d->q_act == DL_ACT_NONE || d->q_act == DL_ACT_RELU || d->q_act == DL_ACT_LRELU);
-    const bool fast3 = d->dtype == DL_F32 && d->prec == DL_PREC_BF16X3 && act_ok3 && d->pad_mode == DL_PAD_ZERO && J >= 256 &&
-                       Ptot >= 32L * d->splitk && (d->p_pstride % 4) == 0 && (d->q_pstride % 4) == 0 && !no_x3;
-    // DL_WGRAD_X3 = "2": the staggered two-phase schedule (wgrad_4ph_x3_kernel), "3": the same without s_setprio.  OFF by default -- measured r03,
-    // same box, ResnetBlock shape, kernel + reduce: 627 us (604 without s_setprio) vs 577 us for the one-barrier kernel; PMC: the stagger
-    // raises the time waves spend parked at barriers / waitcnt (43 % vs 28 % of wave cycles) more than it overlaps (MFMA-busy 31.6 % vs 35.6 %).
+    const bool fast3 = strict && act_ok3 && d->pad_mode == DL_PAD_ZERO && J >= 256 && Ptot >= 32L * d->splitk && (d->p_pstride % 4) == 0 &&
+                       (d->q_pstride % 4) == 0 && dl_switch(DL_SW_NO_X3_GLDS) == nullptr;
+    r.takes_split = fast3 && (d->CAp % 128) == 0;
+    r.split_error = any_split && !(r.takes_split && (!d->p_split || d->p_act == DL_ACT_NONE) && (!d->q_split || d->q_act == DL_ACT_NONE));
+
+    // ---- the ResnetBlock conv (wgrad_w4.h): 3x3, stride 1, image rows of 128 pixels, zero or replicate padding, 128-multiples of channels, 32-bit offsets
+    static const bool no_w4 = DL_DEV_ENV("DL_NO_WGRAD_W4") != nullptr;
+    const size_t rows = (size_t)d->N * d->Hp;
+    const bool w4 = !no_w4 && bf16 && no_act && (d->pad_mode == DL_PAD_ZERO || d->pad_mode == DL_PAD_REPLICATE) && d->KH == 3 && d->KW == 3 && d->step == 1 &&
+                    d->pad == 1 && (d->pad_w < 0 || d->pad_w == 1) && !d->stack_kw && !any_split && d->Wp == 128 && d->Wq == 128 && d->Hp == d->Hq && d->Hp >= 2 &&
+                    d->N >= 1 && (d->CAp % 128) == 0 && (d->CBp % 128) == 0 && (d->p_pstride % 8) == 0 && (d->q_pstride % 8) == 0 &&
+                    rows * 128 * (size_t)d->p_pstride * 2 < ((size_t)1 << 31) && rows * 128 * (size_t)d->q_pstride * 2 < ((size_t)1 << 31) &&
+                    d->splitk >= 1 && (size_t)d->splitk <= rows;
+
+    // Dev-build variants.  DL_WGRAD_8PH=1: the four-phase schedule (wgrad_8ph_kernel).  OFF by default -- measured r02, same box, ResnetBlock shape, kernel +
+    // reduce: 217-225 us vs 191-193 us for the one-barrier kernel in all three variants tried (reads retired before the first barrier; restage two phases later
+    // without forced waits; address arithmetic moved into the MFMA shadow).  The one-barrier kernel alone is 172 us, within 8 % of the forward's 8-phase kernel
+    // (155-160 us), so there was little left to win here.
+    // DL_WGRAD_X3 = "2": the staggered two-phase schedule (wgrad_4ph_x3_kernel), "3": the same without s_setprio.  OFF by default -- measured r03, same box,
+    // ResnetBlock shape, kernel + reduce: 627 us (604 without s_setprio) vs 577 us for the one-barrier kernel; PMC: the stagger raises the time waves spend
+    // parked at barriers / waitcnt (43 % vs 28 % of wave cycles) more than it overlaps (MFMA-busy 31.6 % vs 35.6 %).
+    static const char *w8 = DL_DEV_ENV("DL_WGRAD_8PH");
     static const char *w3 = DL_DEV_ENV("DL_WGRAD_X3");
-    if ((d->p_split || d->q_split) && !(fast3 && (d->CAp % 128) == 0 && (!d->p_split || d->p_act == DL_ACT_NONE) && (!d->q_split || d->q_act == DL_ACT_NONE))) {
-        *err = 1;
-        return WK_GENERIC;
-    }
-    if (w4w_eligible(d)) return WK_W4;
-    if (fast3 && (d->CAp % 256) == 0 && w3 && (w3[0] == '2' || w3[0] == '3') && !d->p_split && !d->q_split) return w3[0] == '3' ? WK_4PH_X3_NOPRIO : WK_4PH_X3;
-    if (fast3 && (d->CAp % 256) == 0) return WK_X3_256;
-    if (fast3 && (d->CAp % 128) == 0) return WK_X3_128;
-    if (fast && (d->CAp % 256) == 0 && w8 && w8[0] == '1') return WK_8PH;
-    if (fast && (d->CAp % 256) == 0) return WK_GLDS256;
-    if (fast && (d->CAp % 128) == 0) return WK_GLDS128;
-    return WK_GENERIC;
+
+    if (r.split_error) r.route = WR_GENERIC;
+    else if (w4) r.route = WR_W4;
+    else if (fast3 && (d->CAp % 256) == 0) {
+        r.route = WR_X3_256;
+        if (w3 && (w3[0] == '2' || w3[0] == '3') && !any_split) r.variant = w3[0] == '3' ? 2 : 1;
+    } else if (fast3 && (d->CAp % 128) == 0) r.route = WR_X3_128;
+    else if (fast && (d->CAp % 256) == 0) {
+        r.route = WR_GLDS256;
+        if (w8 && w8[0] == '1') r.variant = 1;
+    } else if (fast && (d->CAp % 128) == 0) r.route = WR_GLDS128;
+    else r.route = WR_GENERIC;
+
+    const WgradRouteRow &row = g_wgrad_routes[r.route];
+    const int tile_rows = row.rows ? row.rows : wgrad_generic_rows(d->CAp);
+    r.tiles = ((d->CAp + tile_rows - 1) / tile_rows) * ((J + row.cols - 1) / row.cols);
+    r.ksteps = (int)((Ptot + row.kpix - 1) / row.kpix);
+    r.batched = row.batched && !r.variant;
+    return r;
 }
 
-// the split-K kernel of the general path for n same-shaped layers (n > 1: the direct-to-LDS kernels only): slabs only (the reduction is the
-// caller's: immediate or deferred)
-static int wgrad_slabs(const dl_wgrad_desc *d, const WgradLayers &lay, int n, hipStream_t stream, int *J_out) {
-    if (!d) DL_FAIL("dl_conv_wgrad: null descriptor");
-    if (d->N <= 0 || d->Hp <= 0 || d->Wp <= 0 || d->Hq <= 0 || d->Wq <= 0)
-        DL_FAIL("dl_conv_wgrad: empty problem (N=%d, P %dx%d, Q %dx%d): nothing to launch", d->N, d->Hp, d->Wp, d->Hq, d->Wq);
+static int wgrad_split_error(const dl_wgrad_desc *d, const char *who) {
+    DL_FAIL("%s: split-copy operands (p_split / q_split) need the strict direct-to-LDS kernels: fp32 + BF16X3, zero padding, KH*KW*CBp >= 256, "
+            "CAp %% 128 == 0, pixel strides %% 4 == 0, no staged activation on a split operand (CAp=%d, J=%d, p_split=%d, q_split=%d)", who, d->CAp,
+            d->KH * d->KW * d->CBp, d->p_split, d->q_split);
+}
+
+template <typename T, int PREC>
+static int dispatch_wgrad(const WgradArgs &a, hipStream_t stream) {
+    switch (wgrad_generic_rows(a.CAp)) {
+        case 16: return launch_wgrad<T, PREC, 16, 1, 4>(a, stream);
+        case 32: return launch_wgrad<T, PREC, 32, 1, 4>(a, stream);
+        case 64: return launch_wgrad<T, PREC, 64, 2, 2>(a, stream);
+        default: return launch_wgrad<T, PREC, 128, 2, 2>(a, stream);
+    }
+}
+
+// Launches the routed kernel for n same-shaped layers (n > 1: the kernels with a batched form).  The in-place routes also reduce into grad0; every other
+// route leaves d->splitk slabs per layer, whose reduction is the caller's (immediate or deferred).
+static int wgrad_launch(const dl_wgrad_desc *d, const WgradRouted &r, const WgradLayers &lay, int n, float *grad0, hipStream_t stream) {
     if (n < 1 || n > WGRAD_MULTI_MAX) DL_FAIL("dl_conv_wgrad: %d layers in one launch (1 .. %d)", n, WGRAD_MULTI_MAX);
     for (int l = 0; l < n; ++l)
         if (!lay.P[l] || !lay.Q[l] || !lay.slab[l]) DL_FAIL("dl_conv_wgrad: null argument");
+    if (d->N <= 0 || d->Hp <= 0 || d->Wp <= 0 || d->Hq <= 0 || d->Wq <= 0)
+        DL_FAIL("dl_conv_wgrad: empty problem (N=%d, P %dx%d, Q %dx%d): nothing to launch", d->N, d->Hp, d->Wp, d->Hq, d->Wq);
+    if (r.route == WR_C4) return launch_wgrad_c4(d, r.c4_form, lay.P[0], lay.Q[0], grad0, lay.slab[0], stream);
+    if (r.route == WR_C4_X3) return launch_wgrad_c4_x3(d, r.c4_form, lay.P[0], lay.Q[0], grad0, lay.slab[0], stream);
+
     const int l2 = ilog2_exact(d->CBp);
     if (l2 < 3) DL_FAIL("dl_conv_wgrad: CBp=%d must be a power of two >= 8", d->CBp);
     if (d->CAp % 8) DL_FAIL("dl_conv_wgrad: CAp=%d must be a multiple of 8", d->CAp);
@@ -935,6 +1011,8 @@ static int wgrad_slabs(const dl_wgrad_desc *d, const WgradLayers &lay, int n, hi
     if (d->prec == DL_PREC_BF16X3 && d->dtype != DL_F32) DL_FAIL("dl_conv_wgrad: BF16X3 needs fp32 activations");
     if (d->pad_mode < DL_PAD_ZERO || d->pad_mode > DL_PAD_REPLICATE) DL_FAIL("dl_conv_wgrad: pad_mode=%d (0 zero | 1 reflect | 2 replicate)", d->pad_mode);
     if (d->pad_mode == DL_PAD_REPLICATE && d->step != 1) DL_FAIL("dl_conv_wgrad: replicate padding only for step == 1 layers (step=%d)", d->step);
+    if (r.split_error) return wgrad_split_error(d, "dl_conv_wgrad");
+    if (n > 1 && !r.batched) DL_FAIL("dl_conv_wgrad_multi: this descriptor takes a kernel without a batched form (ask dl_wgrad_plan first)");
 
     WgradArgs a;
     memset(&a, 0, sizeof(a));
@@ -946,9 +1024,7 @@ static int wgrad_slabs(const dl_wgrad_desc *d, const WgradLayers &lay, int n, hi
     a.kstride = d->CAp * a.J + wgrad_slab_pad();
     a.Ptot = d->N * d->Hp * d->Wp;
     a.splitk = d->splitk;
-    a.pchunk = ((a.Ptot + d->splitk - 1) / d->splitk + 31) / 32 * 32;
-    const int hw = d->Hp * d->Wp;
-    a.dn = 32 / hw; a.dh = (32 % hw) / d->Wp; a.dw = (32 % hw) % d->Wp;
+    wgrad_pixel_steps(a, 32);            // (the direct-to-LDS launchers set their own K step)
     a.p_act = d->p_act; a.q_act = d->q_act;
     a.p_split = d->p_split; a.q_split = d->q_split;
     static const char *tr_env = DL_DEV_ENV("DL_WGRAD_TR_ASM");            // A/B switch: "0" = the transposing reads through the builtin (rounds 2-4)
@@ -956,37 +1032,20 @@ static int wgrad_slabs(const dl_wgrad_desc *d, const WgradLayers &lay, int n, hi
     static const char *xg_env = DL_DEV_ENV("DL_WGRAD_XCDGROUP");          // A/B switch: "0" keeps the plain 2-D block order
     a.xcd_group = (xg_env && xg_env[0] == '0') ? 0 : 1;
 
-    int err = 0;
-    const int k = wgrad_kernel_of(d, &err);
-    if (err)
-        DL_FAIL("dl_conv_wgrad: split-copy operands need the strict direct-to-LDS kernel (fp32 + BF16X3, zero padding, CAp %% 128 == 0, J >= 256) and no staged activation on them");
-    if (n > 1 && !(k == WK_W4 || k == WK_GLDS256 || k == WK_GLDS128 || k == WK_X3_256 || k == WK_X3_128))
-        DL_FAIL("dl_conv_wgrad_multi: this descriptor takes a kernel without a batched form (ask dl_wgrad_plan first)");
-    int rc;
-    switch (k) {
-        case WK_W4: rc = launch_wgrad_w4(d, lay, n, a.kstride, stream); break;
-        case WK_4PH_X3: rc = launch_wgrad_4ph_x3<0>(a, stream); break;
-        case WK_4PH_X3_NOPRIO: rc = launch_wgrad_4ph_x3<1>(a, stream); break;
-        case WK_X3_256: rc = launch_wgrad_glds_x3<256>(a, lay, n, stream); break;
-        case WK_X3_128: rc = launch_wgrad_glds_x3<128>(a, lay, n, stream); break;
-        case WK_8PH: rc = launch_wgrad_8ph(a, stream); break;
-        case WK_GLDS256: rc = launch_wgrad_glds<256, 2, 4>(a, lay, n, stream); break;
-        case WK_GLDS128: rc = launch_wgrad_glds<128, 2, 4>(a, lay, n, stream); break;
+    switch (r.route) {
+        case WR_W4: return launch_wgrad_w4(d, lay, n, a.kstride, stream);
+        case WR_X3_256:
+            if (r.variant) return r.variant == 2 ? launch_wgrad_4ph_x3<1>(a, stream) : launch_wgrad_4ph_x3<0>(a, stream);
+            return launch_wgrad_glds_x3<256>(a, lay, n, stream);
+        case WR_X3_128: return launch_wgrad_glds_x3<128>(a, lay, n, stream);
+        case WR_GLDS256: return r.variant ? launch_wgrad_8ph(a, stream) : launch_wgrad_glds<256, 2, 4>(a, lay, n, stream);
+        case WR_GLDS128: return launch_wgrad_glds<128, 2, 4>(a, lay, n, stream);
         default:
-            if (d->dtype == DL_BF16 && d->prec == DL_PREC_BF16) rc = dispatch_wgrad<bf16_t, 1>(a, stream);
-            else if (d->dtype == DL_F32 && d->prec == DL_PREC_BF16X3) rc = dispatch_wgrad<float, 3>(a, stream);
-            else if (d->dtype == DL_F32 && d->prec == DL_PREC_BF16) rc = dispatch_wgrad<float, 1>(a, stream);
-            else DL_FAIL("dl_conv_wgrad: unsupported dtype/precision combination");
+            if (d->dtype == DL_BF16 && d->prec == DL_PREC_BF16) return dispatch_wgrad<bf16_t, 1>(a, stream);
+            if (d->dtype == DL_F32 && d->prec == DL_PREC_BF16X3) return dispatch_wgrad<float, 3>(a, stream);
+            if (d->dtype == DL_F32 && d->prec == DL_PREC_BF16) return dispatch_wgrad<float, 1>(a, stream);
+            DL_FAIL("dl_conv_wgrad: unsupported dtype/precision combination");
     }
-    *J_out = a.J;
-    return rc;
-}
-
-static int wgrad_slabs(const dl_wgrad_desc *d, const void *P, const void *Q, float *slab, hipStream_t stream, int *J_out) {
-    if (!P || !Q || !slab) DL_FAIL("dl_conv_wgrad: null argument");
-    WgradLayers lay;
-    lay.P[0] = P; lay.Q[0] = Q; lay.slab[0] = slab;
-    return wgrad_slabs(d, lay, 1, stream, J_out);
 }
 
 // What dl_conv_wgrad / dl_conv_wgrad_multi would run for `d` (d->splitk is ignored except where a kernel's eligibility depends on it: pass 1):
@@ -994,79 +1053,70 @@ static int wgrad_slabs(const dl_wgrad_desc *d, const void *P, const void *Q, flo
 // layer or for a batch.  Returns 1 when the kernel has a batched form (dl_conv_wgrad_multi), 0 when not, < 0 on error.
 extern "C" int dl_wgrad_plan(const dl_wgrad_desc *d, int32_t *tiles, int32_t *ksteps, const char **name) {
     if (!d) DL_FAIL("dl_wgrad_plan: null descriptor");
-    if (wgrad_c4_form(d) || wgrad_c4_x3_form(d)) {
-        if (tiles) *tiles = 0;
-        if (ksteps) *ksteps = 0;
-        if (name) *name = "wgrad_c4";
-        return 0;
-    }
-    int err = 0;
-    const int k = wgrad_kernel_of(d, &err);
-    const int J = d->KH * d->KW * d->CBp;
-    const long Ptot = (long)d->N * d->Hp * d->Wp;
-    int t = 0, ks = 0, multi = 0;
-    const char *nm = "wgrad_kernel";
-    switch (k) {
-        case WK_W4: t = (d->CAp / 128) * (d->CBp / 128) * 3; ks = d->N * d->Hp; multi = 1; nm = "wgrad_w4_kernel"; break;
-        case WK_X3_256: case WK_4PH_X3: case WK_4PH_X3_NOPRIO: t = (d->CAp / 256) * ((J + 255) / 256); ks = (int)((Ptot + 31) / 32); multi = k == WK_X3_256; nm = "wgrad_glds_x3_kernel<256>"; break;
-        case WK_X3_128: t = (d->CAp / 128) * ((J + 255) / 256); ks = (int)((Ptot + 31) / 32); multi = 1; nm = "wgrad_glds_x3_kernel<128>"; break;
-        case WK_GLDS256: case WK_8PH: t = (d->CAp / 256) * ((J + 255) / 256); ks = (int)((Ptot + 63) / 64); multi = k == WK_GLDS256; nm = "wgrad_glds_kernel<256>"; break;
-        case WK_GLDS128: t = (d->CAp / 128) * ((J + 255) / 256); ks = (int)((Ptot + 63) / 64); multi = 1; nm = "wgrad_glds_kernel<128>"; break;
-        default: {
-            const int ba = d->CAp <= 16 ? 16 : (d->CAp <= 32 ? 32 : (d->CAp <= 64 ? 64 : 128));
-            t = ((d->CAp + ba - 1) / ba) * ((J + 127) / 128); ks = (int)((Ptot + 31) / 32);
-        }
-    }
-    if (tiles) *tiles = t;
-    if (ksteps) *ksteps = ks;
-    if (name) *name = nm;
-    if (err)
-        DL_FAIL("dl_wgrad_plan: split-copy operands (p_split / q_split) need the strict direct-to-LDS kernels: fp32 + BF16X3, zero padding, KH*KW*CBp >= 256, "
-                "CAp %% 128 == 0, pixel strides %% 4 == 0, no staged activation on a split operand (CAp=%d, J=%d, p_split=%d, q_split=%d)", d->CAp, J, d->p_split, d->q_split);
-    return multi;
+    const WgradRouted r = wgrad_route(d);
+    if (tiles) *tiles = r.tiles;
+    if (ksteps) *ksteps = r.ksteps;
+    if (name) *name = g_wgrad_routes[r.route].name;
+    return r.split_error ? wgrad_split_error(d, "dl_wgrad_plan") : r.batched;
 }
 
-static int reduce_blocks(const dl_wgrad_desc *d, int J) {
-    if (d->stack_kw == 0 && d->KH * d->KW <= RED_KK_MAX)                    // wgrad_reduce_tiles: one (weight row, 64 channels) item per workgroup pass
-        return (int)min((size_t)RED_MAX_BLOCKS, (size_t)d->CA * ((d->CBp + RED_BCHUNK - 1) / RED_BCHUNK));
-    const size_t total = (size_t)d->CA * (J / 4);
-    return (int)min((size_t)4096, (total + 255) / 256);
+extern "C" int dl_wgrad_route_info(const dl_wgrad_desc *d, dl_wgrad_route *info) {
+    if (!d || !info) DL_FAIL("dl_wgrad_route_info: null argument");
+    const WgradRouted r = wgrad_route(d);
+    info->name = g_wgrad_routes[r.route].name;
+    info->tiles = r.tiles;
+    info->ksteps = r.ksteps;
+    info->batched = r.batched;
+    info->deferrable = !g_wgrad_routes[r.route].in_place;
+    info->takes_split = r.takes_split;
+    info->fixed_splitk = r.c4_form ? DL_WGRAD_C4_PARTS : 0;
+    return r.split_error ? wgrad_split_error(d, "dl_wgrad_route_info") : 0;
+}
+
+extern "C" int dl_conv_wgrad_deferrable(const dl_wgrad_desc *d) {
+    return d && !g_wgrad_routes[wgrad_route(d).route].in_place;
+}
+
+// the pending reduction of one layer's slabs (dl_wgrad_reduce_batch's record; dl_conv_wgrad's immediate reduction takes its arguments from it too)
+static dl_wgrad_reduce_entry wgrad_reduce_entry_of(const dl_wgrad_desc *d, float *slab, float *grad) {
+    dl_wgrad_reduce_entry e;
+    memset(&e, 0, sizeof(e));
+    e.slab = slab; e.grad = grad;
+    e.splitk = d->splitk; e.CAp = d->CAp; e.CBp = d->CBp; e.J = d->KH * d->KW * d->CBp; e.CA = d->CA; e.CB = d->CB; e.KK = d->KH * d->KW;
+    e.accumulate = d->accumulate; e.stack_kw = d->stack_kw;
+    e.block0 = 0; e.kstride = d->CAp * e.J + wgrad_slab_pad();
+    if (d->stack_kw == 0 && e.KK <= RED_KK_MAX)                              // wgrad_reduce_tiles: one (weight row, 64 channels) item per workgroup pass
+        e.nblocks = (int)min((size_t)RED_MAX_BLOCKS, (size_t)d->CA * ((d->CBp + RED_BCHUNK - 1) / RED_BCHUNK));
+    else e.nblocks = (int)min((size_t)4096, ((size_t)d->CA * (e.J / 4) + 255) / 256);
+    return e;
 }
 
 extern "C" int dl_conv_wgrad(const dl_wgrad_desc *d, const void *P, const void *Q, float *grad, float *slab, void *stream_) {
     hipStream_t stream = (hipStream_t)stream_;
     if (!d) DL_FAIL("dl_conv_wgrad: null descriptor");
     if (!grad) DL_FAIL("dl_conv_wgrad: null argument");
-    if (d->N > 0 && d->Hp > 0 && d->Wp > 0 && P && Q && slab) {
-        if (const int form = wgrad_c4_form(d)) return launch_wgrad_c4(d, form, P, Q, grad, slab, stream);
-        if (const int form = wgrad_c4_x3_form(d)) return launch_wgrad_c4_x3(d, form, P, Q, grad, slab, stream);
-    }
-    int J = 0;
-    if (const int rc = wgrad_slabs(d, P, Q, slab, stream, &J)) return rc;
-    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(reduce_blocks(d, J)), dim3(256), 0, stream, slab, d->splitk, d->CAp * J + wgrad_slab_pad(), d->CBp, J, d->CA, d->CB,
-                       d->KH * d->KW, grad, d->accumulate, d->stack_kw);
+    const WgradRouted r = wgrad_route(d);
+    WgradLayers lay;
+    lay.P[0] = P; lay.Q[0] = Q; lay.slab[0] = slab;
+    if (const int rc = wgrad_launch(d, r, lay, 1, grad, stream)) return rc;
+    if (g_wgrad_routes[r.route].in_place) return 0;
+    const dl_wgrad_reduce_entry e = wgrad_reduce_entry_of(d, slab, grad);
+    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(e.nblocks), dim3(256), 0, stream, e.slab, e.splitk, e.kstride, e.CBp, e.J, e.CA, e.CB, e.KK, e.grad, e.accumulate,
+                       e.stack_kw);
     DL_CHECK_LAUNCH("dl_conv_wgrad(reduce)");
     return 0;
-}
-
-extern "C" int dl_conv_wgrad_deferrable(const dl_wgrad_desc *d) {
-    return d && !wgrad_c4_form(d) && !wgrad_c4_x3_form(d);
 }
 
 extern "C" int dl_conv_wgrad_slabs(const dl_wgrad_desc *d, const void *P, const void *Q, float *grad, float *slab, dl_wgrad_reduce_entry *entry_host,
                                    void *stream_) {
     hipStream_t stream = (hipStream_t)stream_;
     if (!d || !entry_host || !grad) DL_FAIL("dl_conv_wgrad_slabs: null argument");
-    if (!dl_conv_wgrad_deferrable(d)) DL_FAIL("dl_conv_wgrad_slabs: the persistent narrow-channel kernels reduce in place; call dl_conv_wgrad");
-    int J = 0;
-    if (const int rc = wgrad_slabs(d, P, Q, slab, stream, &J)) return rc;
-    dl_wgrad_reduce_entry e;
-    memset(&e, 0, sizeof(e));
-    e.slab = slab; e.grad = grad;
-    e.splitk = d->splitk; e.CAp = d->CAp; e.CBp = d->CBp; e.J = J; e.CA = d->CA; e.CB = d->CB; e.KK = d->KH * d->KW;
-    e.accumulate = d->accumulate; e.stack_kw = d->stack_kw;
-    e.block0 = 0; e.nblocks = reduce_blocks(d, J); e.kstride = d->CAp * J + wgrad_slab_pad();
-    *entry_host = e;
+    const WgradRouted r = wgrad_route(d);
+    if (g_wgrad_routes[r.route].in_place) DL_FAIL("dl_conv_wgrad_slabs: the persistent narrow-channel kernels reduce in place; call dl_conv_wgrad");
+    WgradLayers lay;
+    lay.P[0] = P; lay.Q[0] = Q; lay.slab[0] = slab;
+    if (const int rc = wgrad_launch(d, r, lay, 1, grad, stream)) return rc;
+    *entry_host = wgrad_reduce_entry_of(d, slab, grad);
     return 0;
 }
 
@@ -1077,24 +1127,16 @@ extern "C" int dl_conv_wgrad_multi(const dl_wgrad_desc *d, int n, const void *co
     hipStream_t stream = (hipStream_t)stream_;
     if (!d || !P || !Q || !grad || !slab || !entries_host) DL_FAIL("dl_conv_wgrad_multi: null argument");
     if (n < 1 || n > WGRAD_MULTI_MAX) DL_FAIL("dl_conv_wgrad_multi: n=%d (1 .. %d)", n, WGRAD_MULTI_MAX);
-    if (!dl_conv_wgrad_deferrable(d)) DL_FAIL("dl_conv_wgrad_multi: the persistent narrow-channel kernels reduce in place; call dl_conv_wgrad");
+    const WgradRouted r = wgrad_route(d);
+    if (g_wgrad_routes[r.route].in_place) DL_FAIL("dl_conv_wgrad_multi: the persistent narrow-channel kernels reduce in place; call dl_conv_wgrad");
     const size_t per_layer = dl_wgrad_slab_floats(d);
     WgradLayers lay;
     for (int l = 0; l < n; ++l) {
         if (!grad[l]) DL_FAIL("dl_conv_wgrad_multi: null gradient");
         lay.P[l] = P[l]; lay.Q[l] = Q[l]; lay.slab[l] = slab + (size_t)l * per_layer;
     }
-    int J = 0;
-    if (const int rc = wgrad_slabs(d, lay, n, stream, &J)) return rc;
-    for (int l = 0; l < n; ++l) {
-        dl_wgrad_reduce_entry e;
-        memset(&e, 0, sizeof(e));
-        e.slab = lay.slab[l]; e.grad = grad[l];
-        e.splitk = d->splitk; e.CAp = d->CAp; e.CBp = d->CBp; e.J = J; e.CA = d->CA; e.CB = d->CB; e.KK = d->KH * d->KW;
-        e.accumulate = d->accumulate; e.stack_kw = d->stack_kw;
-        e.block0 = 0; e.nblocks = reduce_blocks(d, J); e.kstride = d->CAp * J + wgrad_slab_pad();
-        entries_host[l] = e;
-    }
+    if (const int rc = wgrad_launch(d, r, lay, n, grad[0], stream)) return rc;
+    for (int l = 0; l < n; ++l) entries_host[l] = wgrad_reduce_entry_of(d, lay.slab[l], grad[l]);
     return 0;
 }
 

@@ -172,17 +172,6 @@ __global__ void __launch_bounds__(256) wgrad_c4_reduce_kernel(const float *slab,
     *g = (accumulate ? *g : 0.f) + (float)tot;
 }
 
-#define DL_WGRAD_C4_PARTS 512
-static int wgrad_c4_form(const dl_wgrad_desc *d) {          // 0: not eligible, 1: P wide / Q small (stem), 2: P small / Q wide (head)
-    const bool off = dl_switch_is_one(DL_SW_NO_WGRAD_C4);       // "1" switches the kernel off (same parse as deepliif_amd/ops.py)
-    if (off || d->dtype != DL_BF16 || d->prec != DL_PREC_BF16 || d->p_act != DL_ACT_NONE || d->q_act != DL_ACT_NONE) return 0;
-    if (d->KH != 7 || d->KW != 7 || d->step != 1 || d->pad != 3 || (d->pad_w >= 0 && d->pad_w != 3) || d->pad_mode != DL_PAD_ZERO || d->stack_kw) return 0;
-    if (d->Hp != d->Hq || d->Wp != d->Wq || d->Hp % 4 || d->Wp % 64 || d->splitk != DL_WGRAD_C4_PARTS) return 0;
-    if (d->CAp == 64 && d->CA <= 64 && d->CBp == 8 && d->CB <= 4) return 1;
-    if (d->CAp == 8 && d->CA <= 4 && d->CBp == 64 && d->CB <= 64) return 2;
-    return 0;
-}
-
 static int launch_wgrad_c4(const dl_wgrad_desc *d, int form, const void *P, const void *Q, float *grad, float *slab, hipStream_t stream) {
     WgradC4Args a;
     a.wide = (const bf16_t *)(form == 1 ? P : Q);

@@ -256,20 +256,6 @@ __global__ void __launch_bounds__(256) wgrad_w4_kernel(const WgradW4Args a, cons
         }
 }
 
-// the layers this kernel serves (see the header comment)
-static bool w4w_eligible(const dl_wgrad_desc *d) {
-    static const bool off = DL_DEV_ENV("DL_NO_WGRAD_W4") != nullptr;
-    if (off) return false;
-    if (d->dtype != DL_BF16 || d->prec != DL_PREC_BF16 || d->p_act != DL_ACT_NONE || d->q_act != DL_ACT_NONE) return false;
-    if (d->pad_mode != DL_PAD_ZERO && d->pad_mode != DL_PAD_REPLICATE) return false;
-    if (d->KH != 3 || d->KW != 3 || d->step != 1 || d->pad != 1 || (d->pad_w >= 0 && d->pad_w != 1) || d->stack_kw || d->p_split || d->q_split) return false;
-    if (d->Wp != 128 || d->Wq != 128 || d->Hp != d->Hq || d->Hp < 2 || d->N < 1) return false;
-    if ((d->CAp % 128) || (d->CBp % 128) || (d->p_pstride % 8) || (d->q_pstride % 8)) return false;
-    const size_t rows = (size_t)d->N * d->Hp;
-    if (rows * 128 * (size_t)d->p_pstride * 2 >= ((size_t)1 << 31) || rows * 128 * (size_t)d->q_pstride * 2 >= ((size_t)1 << 31)) return false;   // 32-bit offsets
-    return d->splitk >= 1 && (size_t)d->splitk <= rows;
-}
-
 static int launch_wgrad_w4(const dl_wgrad_desc *d, const WgradLayers &lay, int n, int kstride, hipStream_t stream) {
     WgradW4Args a;
     memset(&a, 0, sizeof(a));
@@ -281,11 +267,7 @@ static int launch_wgrad_w4(const dl_wgrad_desc *d, const WgradLayers &lay, int n
     const bool copy = d->pad_mode == DL_PAD_REPLICATE;
     auto kern = copy ? wgrad_w4_kernel<DL_PAD_REPLICATE> : wgrad_w4_kernel<DL_PAD_ZERO>;
     static bool attr_set[2] = {false, false};
-    if (!attr_set[copy]) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)W4W_LDS);
-        if (e != hipSuccess) DL_FAIL("dl_conv_wgrad(w4): hipFuncSetAttribute(%zu): %s", W4W_LDS, hipGetErrorString(e));
-        attr_set[copy] = true;
-    }
+    if (wgrad_lds_limit(reinterpret_cast<const void *>(kern), W4W_LDS, &attr_set[copy], "dl_conv_wgrad(w4)")) return -1;
     const int grid = a.tiles_a * a.tiles_b * 3 * a.splitk * n;
     hipLaunchKernelGGL(kern, dim3(grid), dim3(256), W4W_LDS, stream, a, lay);
     DL_CHECK_LAUNCH("dl_conv_wgrad(w4)");

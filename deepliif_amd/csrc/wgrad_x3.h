@@ -509,16 +509,10 @@ static int launch_wgrad_4ph_x3(WgradArgs a, hipStream_t stream) {
     constexpr size_t smem = (size_t)2 * 32 * (256 + 256) * sizeof(float);
     a.tiles_a = a.CAp / 256;
     a.tiles_j = (a.J + 255) / 256;
-    a.pchunk = ((a.Ptot + a.splitk - 1) / a.splitk + 31) / 32 * 32;
-    const int hw = a.Hp * a.Wp;
-    a.dn = 32 / hw; a.dh = (32 % hw) / a.Wp; a.dw = (32 % hw) % a.Wp;
+    wgrad_pixel_steps(a, 32);
     auto kern = wgrad_4ph_x3_kernel<NOPRIO>;
     static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-        if (e != hipSuccess) DL_FAIL("dl_conv_wgrad: hipFuncSetAttribute: %s", hipGetErrorString(e));
-        attr_set = true;
-    }
+    if (wgrad_lds_limit(reinterpret_cast<const void *>(kern), smem, &attr_set, "dl_conv_wgrad(4-phase x3)")) return -1;
     hipLaunchKernelGGL(kern, dim3(a.tiles_a * a.tiles_j, a.splitk), dim3(512), smem, stream, a);
     DL_CHECK_LAUNCH("dl_conv_wgrad(4-phase x3)");
     return 0;
@@ -529,16 +523,10 @@ static int launch_wgrad_glds_x3_v(WgradArgs a, const WgradLayers &lay, int n, hi
     constexpr size_t smem = (size_t)2 * 32 * (BA + 256) * sizeof(float);
     a.tiles_a = a.CAp / BA;
     a.tiles_j = (a.J + 255) / 256;
-    a.pchunk = ((a.Ptot + a.splitk - 1) / a.splitk + 31) / 32 * 32;
-    const int hw = a.Hp * a.Wp;
-    a.dn = 32 / hw; a.dh = (32 % hw) / a.Wp; a.dw = (32 % hw) % a.Wp;
+    wgrad_pixel_steps(a, 32);
     auto kern = wgrad_glds_x3_kernel<BA, TRASM>;
     static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-        if (e != hipSuccess) DL_FAIL("dl_conv_wgrad: hipFuncSetAttribute: %s", hipGetErrorString(e));
-        attr_set = true;
-    }
+    if (wgrad_lds_limit(reinterpret_cast<const void *>(kern), smem, &attr_set, "dl_conv_wgrad(glds x3)")) return -1;
     hipLaunchKernelGGL(kern, dim3(a.tiles_a * a.tiles_j, a.splitk, n), dim3(512), smem, stream, a, lay);
     DL_CHECK_LAUNCH("dl_conv_wgrad(glds x3)");
     return 0;
@@ -676,16 +664,6 @@ __global__ void __launch_bounds__(256, 2) wgrad_c4_x3_kernel(const WgradC4X3Args
         }
 }
 
-static int wgrad_c4_x3_form(const dl_wgrad_desc *d) {          // as wgrad_c4_form, for fp32 operands + BF16X3
-    const bool off = dl_switch_is_one(DL_SW_NO_WGRAD_C4) || dl_switch(DL_SW_NO_C4_X3) != nullptr;
-    if (off || d->dtype != DL_F32 || d->prec != DL_PREC_BF16X3 || d->p_act != DL_ACT_NONE || d->q_act != DL_ACT_NONE || d->p_split || d->q_split) return 0;
-    if (d->KH != 7 || d->KW != 7 || d->step != 1 || d->pad != 3 || (d->pad_w >= 0 && d->pad_w != 3) || d->pad_mode != DL_PAD_ZERO || d->stack_kw) return 0;
-    if (d->Hp != d->Hq || d->Wp != d->Wq || d->Hp % 4 || d->Wp % 64 || d->splitk != DL_WGRAD_C4_PARTS) return 0;
-    if (d->CAp == 64 && d->CA <= 64 && d->CBp == 8 && d->CB <= 4) return 1;
-    if (d->CAp == 8 && d->CA <= 4 && d->CBp == 64 && d->CB <= 64) return 2;
-    return 0;
-}
-
 static int launch_wgrad_c4_x3(const dl_wgrad_desc *d, int form, const void *P, const void *Q, float *grad, float *slab, hipStream_t stream) {
     WgradC4X3Args a;
     a.wide = (const float *)(form == 1 ? P : Q);
@@ -699,11 +677,7 @@ static int launch_wgrad_c4_x3(const dl_wgrad_desc *d, int form, const void *P, c
     const int parts = ntiles < DL_WGRAD_C4_PARTS ? ntiles : DL_WGRAD_C4_PARTS;
     constexpr size_t smem = (size_t)(2 * 2 * 64 * 80 + 2 * (8 * 72 * 4 + 32)) * sizeof(bf16_t);
     static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(wgrad_c4_x3_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-        if (e != hipSuccess) DL_FAIL("dl_conv_wgrad(c4 x3): hipFuncSetAttribute: %s", hipGetErrorString(e));
-        attr_set = true;
-    }
+    if (wgrad_lds_limit(reinterpret_cast<const void *>(wgrad_c4_x3_kernel), smem, &attr_set, "dl_conv_wgrad(c4 x3)")) return -1;
     hipLaunchKernelGGL(wgrad_c4_x3_kernel, dim3(parts), dim3(256), smem, stream, a);
     DL_CHECK_LAUNCH("dl_conv_wgrad(c4 x3)");
     hipLaunchKernelGGL(wgrad_c4_reduce_kernel, dim3(64 * 56 / 8), dim3(256), 0, stream, slab, parts, grad, d->CA, d->CB, form == 1 ? 1 : 0, d->accumulate);

@@ -235,34 +235,18 @@ WGRAD_FILL = float(os.environ.get('DL_WGRAD_FILL', '1.0'))               # one l
 WGRAD_BATCH_FILL = float(os.environ.get('DL_WGRAD_BATCH_FILL', '0.3333'))    # a layer inside a batch (choose_wgrad_batch_splitk)
 
 
-def wgrad_fast_path(cap: int, j: int, bf16: bool, no_act: bool, zero_pad: bool, strict: bool = False, strict_act_ok: bool = True) -> bool:
-    """mirror of the dispatch predicates in wgrad.hip: the direct-to-LDS 8-wave kernels -- wgrad_glds_kernel (bf16 policy, no staged
-    activation) and wgrad_glds_x3_kernel (strict policy = fp32 storage + split-bf16 x3; relu / lrelu on an operand are applied while the
-    tile is split in LDS, csrc/wgrad_x3.h)"""
-    shape_ok = zero_pad and j >= 256 and cap % 128 == 0
-    return shape_ok and ((bf16 and no_act) or (strict and strict_act_ok))
-
-
-def choose_wgrad_splitk(cap: int, j: int, ptot: int, fast: bool = False, target_blocks: int = 1024, max_split: int = 256) -> int:
-    if fast:
-        # 8-wave kernel: one workgroup per CU (248 VGPRs) -> the grid must not exceed one round of 256 CUs by a few blocks
-        ba = 256 if cap % 256 == 0 else 128
-        tiles = (cap // ba) * ((j + 255) // 256)
+def choose_wgrad_splitk(kernel: str, tiles: int, ksteps: int, ptot: int, target_blocks: int = 1024, max_split: int = 256) -> int:
+    """split-K of one layer per launch, from what the library says it will run (dl_wgrad_route_info at splitk = 1: kernel name, output tiles, K steps)"""
+    if kernel == 'wgrad_w4_kernel':
+        return max(1, min(NUM_CUS // tiles, ksteps))       # 12 tiles x 21 row ranges = 252 workgroups: one round of the chip
+    if kernel.startswith('wgrad_glds'):
+        # 8-wave direct-to-LDS kernels: one workgroup per CU (248 VGPRs) -> the grid must not exceed one round of 256 CUs by a few blocks
         cus = max(1, int(NUM_CUS * WGRAD_FILL))
         if tiles >= cus:
             return 1
         return max(1, min(cus // tiles, ptot // 128, max_split))
-    ba = 16 if cap <= 16 else (64 if cap <= 64 else 128)
-    tiles = ((cap + ba - 1) // ba) * ((j + 127) // 128)
     sk = min(max_split, (target_blocks + tiles - 1) // tiles, max(1, ptot // 64))
     return max(1, sk)
-
-
-def wgrad_batch_shape(kh: int, kw: int, step: int, wp: int, hp: int, hq: int, cap: int, cbp: int) -> bool:
-    """the layers ops.HipBackend queues for the batched weight gradient: the ResnetBlock conv (networks.py:467-513) -- 3x3, stride 1, image rows of 128 pixels --
-    i.e. the one shape a network repeats (18 times in a Resnet-9).  Every other layer occurs once per network and pass: a batch of one would only
-    under-fill the chip with the batch's small split-K."""
-    return kh == 3 and kw == 3 and step == 1 and wp == 128 and hp == hq and cap % 128 == 0 and cbp % 128 == 0
 
 
 def choose_wgrad_batch_splitk(tiles: int, ksteps: int) -> int:
@@ -273,14 +257,4 @@ def choose_wgrad_batch_splitk(tiles: int, ksteps: int) -> int:
     return max(1, min((int(NUM_CUS * WGRAD_BATCH_FILL) + tiles // 2) // tiles, max(1, ksteps // 16)))
 
 
-WGRAD_C4_PARTS = 512
-
-
-def wgrad_c4_ok(cap: int, ca: int, cbp: int, cb: int, k: int, step: int, pad: int, pad_mode: int, hp: int, wp: int, hq: int, wq: int, bf16: bool,
-                no_act: bool, stacked: bool) -> bool:
-    """mirror of wgrad_c4_form (csrc/wgrad_c4.h): the 7x7 weight gradient with one 64-channel and one <= 4-channel operand (Resnet stem / head)"""
-    if not (bf16 and no_act) or stacked or k != 7 or step != 1 or pad != 3 or pad_mode != L.PAD_ZERO:
-        return False
-    if (hp, wp) != (hq, wq) or hp % 4 or wp % 64:
-        return False
-    return (cap == 64 and cbp == 8 and cb <= 4) or (cap == 8 and ca <= 4 and cbp == 64)
+WGRAD_C4_PARTS = L.WGRAD_C4_PARTS       # (defined with the other ABI constants in _lib.py; importers of its earlier home here keep working)

@@ -21,8 +21,7 @@ from typing import Optional
 import torch
 
 from . import _lib as L
-from .geometry import (GatherPlan, NUM_CUS, WGRAD_C4_PARTS, choose_splitk, choose_wgrad_batch_splitk, choose_wgrad_splitk, fill_conv_desc, fill_pack_desc,
-                       wgrad_batch_shape, wgrad_c4_ok, wgrad_fast_path)
+from .geometry import GatherPlan, choose_splitk, choose_wgrad_batch_splitk, choose_wgrad_splitk, fill_conv_desc, fill_pack_desc
 
 
 def dl_dtype(t: torch.Tensor) -> int:
@@ -40,17 +39,25 @@ def pstride(t: torch.Tensor) -> int:
     return ps
 
 
+def wgrad_desc(P: torch.Tensor, Q: torch.Tensor, grad: torch.Tensor, k: int, step: int, pad: int, pad_mode: int, p_act: int, q_act: int, prec: int,
+               accumulate: bool = False, stack_kw: int = 0, p_split: bool = False, q_split: bool = False, splitk: int = 1) -> L.WgradDesc:
+    """the dl_wgrad_desc of one weight gradient; reads shapes, strides and dtypes only (tensors on `meta` will do)"""
+    n, hp, wp, cap = P.shape
+    _, hq, wq, cbp = Q.shape
+    ca, kw, pad_w = (grad.shape[0] * stack_kw, 1, 0) if stack_kw else (grad.shape[0], k, -1)
+    return L.WgradDesc(N=n, Hp=hp, Wp=wp, CAp=cap, p_pstride=pstride(P), Hq=hq, Wq=wq, CBp=cbp, q_pstride=pstride(Q), KH=k, KW=kw, step=step, pad=pad,
+                       pad_mode=pad_mode, CA=ca, CB=grad.shape[1], dtype=dl_dtype(P), prec=prec, splitk=splitk, accumulate=1 if accumulate else 0,
+                       q_act=q_act, p_act=p_act, pad_w=pad_w, stack_kw=stack_kw, p_split=1 if p_split else 0, q_split=1 if q_split else 0)
+
+
 _SHARED_SCRATCH = os.environ.get('DL_SHARED_SCRATCH', '0') == '1'
 # DL_BNSTATS=1: the data gradient's store epilogue also produces the following norm backward's reductions (dl_conv_forward_bnstats).  OFF by
 # default: same-box A/B of the training step (r02) 104.9-105.0 ms with it vs 103.8-104.0 without -- the y tile read sits exposed in the
 # epilogue of a 1-workgroup-per-CU kernel (+37 us per fused ResnetBlock launch) and costs what the saved pass (49 us) was worth.
 _BNSTATS = os.environ.get('DL_BNSTATS', '0') == '1'
 _CONV_ADD = os.environ.get('DL_CONV_ADD', '1') != '0'      # A/B switch (Python side only): 0 = a second gradient contribution is always added by dl_axpby
-_NO_WGRAD_C4 = os.environ.get('DL_NO_WGRAD_C4', '0') == '1'
-_NO_X3_GLDS = os.environ.get('DL_NO_X3_GLDS') is not None           # A/B switch: the strict policy on the round-1 register-staged kernels (csrc reads the same variable)
-_X3_ACTS = (L.ACT_NONE, L.ACT_RELU, L.ACT_LRELU)
+_NO_X3_GLDS = os.environ.get('DL_NO_X3_GLDS') is not None           # A/B switch: the strict policy on the round-1 register-staged kernels (conv_takes_split; csrc reads the same variable)
 _SPLIT_ONLY_GRAD = os.environ.get('DL_NO_SPLIT_ONLY_GRAD', '0') != '1'     # A/B switch: 1 = the norm backward always stores the fp32 gradient next to its split copy
-_NO_C4_X3 = 'DL_NO_C4_X3' in os.environ              # A/B switch: the strict 7x7 stem / head on the general x3 kernels (csrc/conv_x3.h, wgrad_x3.h)
 _WGRAD_DEFER = os.environ.get('DL_WGRAD_DEFER', '1') != '0'            # A/B switch: 0 = every weight gradient reduces its slabs right behind the split-K kernel (rounds 1-3)
 # slab arena of the deferred reduction, per scratch state (thread / branch stream): grown on demand, never below this.  r04 reserved 4 GB per state whatever the
 # model (ADVICE r4: ~16 GB with three branch streams, also for an ngf = 8 fixture); since the batched weight gradient (below) a Resnet-9 pass at batch 8 writes
@@ -451,52 +458,44 @@ class HipBackend:
         return True
 
     # ---- weight gradient
+    def wgrad_route(self, d: L.WgradDesc) -> L.WgradRoute:
+        """what csrc/wgrad.hip wgrad_route() chooses for the descriptor (d.splitk = 1: the kernel split-K is then sized for).  The answer is a function of the
+        descriptor and the library's switches: it is remembered per descriptor in the library object's memo, which dl_switches_reload() empties (_lib.load)."""
+        memo = getattr(self.lib, 'wgrad_route_memo', None)
+        key = bytes(d)
+        r = memo.get(key) if memo is not None else None
+        if r is None:
+            r = L.WgradRoute()
+            self.check(self.lib.dl_wgrad_route_info(C.byref(d), C.byref(r)), 'dl_wgrad_route_info')
+            if memo is not None:
+                if len(memo) >= 4096:
+                    memo.clear()
+                memo[key] = r
+        return r
+
     def conv_wgrad(self, P: torch.Tensor, Q: torch.Tensor, grad: torch.Tensor, k: int, step: int, pad: int, pad_mode: int,
                    p_act: int, q_act: int, prec: int, accumulate: bool, splitk: Optional[int] = None, stack_kw: int = 0, p_split: bool = False,
                    q_split: bool = False):
         """stack_kw > 0: P is a dl_shift_stack image (channel = a*stack_kw + kw); vertical taps only (KH = k, KW = 1)"""
         _need_cuda(P, Q, grad)
         assert grad.dtype == torch.float32 and grad.is_contiguous()
-        d = L.WgradDesc()
-        d.N, d.Hp, d.Wp, d.CAp = P.shape
-        d.p_pstride = pstride(P)
-        _, d.Hq, d.Wq, d.CBp = Q.shape
-        d.q_pstride = pstride(Q)
-        d.KH = d.KW = k
-        d.step, d.pad, d.pad_mode = step, pad, pad_mode
-        d.CA, d.CB = grad.shape[0], grad.shape[1]
-        d.pad_w, d.stack_kw = -1, 0
-        if stack_kw:
-            d.KW, d.pad_w, d.stack_kw, d.CA = 1, 0, stack_kw, grad.shape[0] * stack_kw
-        d.dtype, d.prec = dl_dtype(P), prec
-        d.accumulate = 1 if accumulate else 0
-        d.p_act, d.q_act = p_act, q_act
-        d.p_split, d.q_split = (1 if p_split else 0), (1 if q_split else 0)
-        j = d.KH * d.KW * d.CBp
-        strict = d.dtype == L.DL_F32 and prec == L.PREC_BF16X3 and not _NO_X3_GLDS
-        fast = wgrad_fast_path(d.CAp, j, d.dtype == L.DL_BF16 and prec == L.PREC_BF16, p_act == L.ACT_NONE and q_act == L.ACT_NONE,
-                               pad_mode == L.PAD_ZERO, strict, p_act in _X3_ACTS and q_act in _X3_ACTS)
-        # which kernel will run (the library decides: csrc/wgrad.hip wgrad_kernel_of), with its tile count -- split-K is sized from that
-        d.splitk = 1
-        tiles, ksteps, kname = L.i32(), L.i32(), C.c_char_p()
-        multi = int(self.lib.dl_wgrad_plan(C.byref(d), C.byref(tiles), C.byref(ksteps), C.byref(kname)))
-        if multi < 0:
-            self.check(multi, 'dl_wgrad_plan')
-        w4 = kname.value == b'wgrad_w4_kernel'
+        d = wgrad_desc(P, Q, grad, k, step, pad, pad_mode, p_act, q_act, prec, accumulate, stack_kw, p_split, q_split)
+        r = self.wgrad_route(d)             # which kernel will run, with its tile count -- split-K is sized from that
+        kernel = r.name.decode()
         deferring = _WGRAD_DEFER and WS._thread_state().get('defer_depth', 0) > 0
-        # batched: the w4 kernel's layers only.  Measured r05 (profiles/r05/wgrad_first_look.txt, 18 layers): bf16 w4 129.6 -> 114.3 us per layer; the strict
-        # glds_x3 kernel 465.5 -> 473.2 (its 3 x MFMA work already hides the slab store; split-K 9 instead of 28 only lengthens the tail)
-        if deferring and _WGRAD_BATCH and splitk is None and multi == 1 and w4 and wgrad_batch_shape(d.KH, d.KW, d.step, d.Wp, d.Hp, d.Hq, d.CAp, d.CBp):
-            self._wgrad_queued(WS._state(), d, P, Q, grad, tiles.value, ksteps.value)
+        # batched: the w4 kernel's layers only (the ResnetBlock conv, the one shape a network repeats: 18 times in a Resnet-9; every other layer occurs once per
+        # network and pass, and a batch of one would only under-fill the chip with the batch's small split-K).  Measured r05 (profiles/r05/wgrad_first_look.txt,
+        # 18 layers): bf16 w4 129.6 -> 114.3 us per layer; the strict glds_x3 kernel 465.5 -> 473.2 (its 3 x MFMA work already hides the slab store; split-K 9
+        # instead of 28 only lengthens the tail)
+        if deferring and _WGRAD_BATCH and splitk is None and r.batched and kernel == 'wgrad_w4_kernel':
+            self._wgrad_queued(WS._state(), d, P, Q, grad, r.tiles, r.ksteps)
             return
         if splitk is not None:
             d.splitk = splitk
-        elif w4:
-            d.splitk = max(1, min(NUM_CUS // tiles.value, ksteps.value))       # 12 tiles x 21 row ranges = 252 workgroups: one round of the chip
+        elif r.fixed_splitk:
+            d.splitk = r.fixed_splitk           # the persistent 7x7 stem / head kernels: one partial result per workgroup (csrc/wgrad_c4.h)
         else:
-            d.splitk = choose_wgrad_splitk(d.CAp, j, d.N * d.Hp * d.Wp, fast)
-        if splitk is None and not _NO_WGRAD_C4 and self.wgrad_c4_applies(P, Q, grad, k, step, pad, pad_mode, p_act, q_act, prec, stack_kw):
-            d.splitk = WGRAD_C4_PARTS          # one partial result per persistent workgroup (csrc/wgrad_c4.h)
+            d.splitk = choose_wgrad_splitk(kernel, r.tiles, r.ksteps, d.N * d.Hp * d.Wp)
         nslab = int(self.lib.dl_wgrad_slab_floats(C.byref(d)))
         if deferring and self.lib.dl_conv_wgrad_deferrable(C.byref(d)):
             self._wgrad_deferred(WS._state(), d, P, Q, grad, nslab)
@@ -645,16 +644,15 @@ class HipBackend:
         return (self.supports_split and not _NO_X3_GLDS and x.dtype == torch.float32 and prec == L.PREC_BF16X3 and in_act == L.ACT_NONE)
 
     def wgrad_takes_split(self, P, Q, grad, k, pad_mode, prec, stack_kw=0) -> bool:
-        """mirror of the fast3 predicate in wgrad.hip: strict direct-to-LDS weight gradient"""
-        if not self.supports_split or _NO_X3_GLDS or stack_kw or P.dtype != torch.float32 or prec != L.PREC_BF16X3 or pad_mode != L.PAD_ZERO:
+        """does a strict direct-to-LDS weight-gradient kernel serve this layer, i.e. can conv_wgrad read split copies of its operands?  (The answer does not
+        depend on stride and padding; a shift-stacked P is built per call and has no split copy.)"""
+        if not self.supports_split or stack_kw:
             return False
-        cap, j, ptot = P.shape[3], k * k * Q.shape[3], P.shape[0] * P.shape[1] * P.shape[2]
-        return cap % 128 == 0 and j >= 256 and ptot >= 32 * choose_wgrad_splitk(cap, j, ptot, True)
+        return bool(self.wgrad_route(wgrad_desc(P, Q, grad, k, 1, 0, pad_mode, L.ACT_NONE, L.ACT_NONE, prec)).takes_split)
 
     def wgrad_c4_applies(self, P, Q, grad, k, step, pad, pad_mode, p_act, q_act, prec, stack_kw=0) -> bool:
-        return not _NO_WGRAD_C4 and wgrad_c4_ok(P.shape[3], grad.shape[0], Q.shape[3], grad.shape[1], k, step, pad, pad_mode, P.shape[1], P.shape[2], Q.shape[1], Q.shape[2],
-                           (P.dtype == torch.bfloat16 and prec == L.PREC_BF16) or (P.dtype == torch.float32 and prec == L.PREC_BF16X3 and not _NO_C4_X3),
-                           p_act == L.ACT_NONE and q_act == L.ACT_NONE, bool(stack_kw))
+        """is this the 7x7 stem / head that conv_wgrad (automatic split-K) hands to the persistent narrow-channel kernels (csrc/wgrad_c4.h)?"""
+        return bool(self.wgrad_route(wgrad_desc(P, Q, grad, k, step, pad, pad_mode, p_act, q_act, prec, stack_kw=stack_kw)).fixed_splitk)
 
     # ---- normalisation
     def _norm_desc(self, y, C_real, scope, act, momentum, z_ps, r_ps):

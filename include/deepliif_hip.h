@@ -51,6 +51,7 @@ enum { DL_LOSS_BCE_LOGITS = 0, DL_LOSS_MSE = 1, DL_LOSS_SMOOTH_L1 = 2, DL_LOSS_L
 #define DL_MAX_TAPS 64
 #define DL_MAX_PHASES 4
 #define DL_WGRAD_MULTI_MAX 24       /* layers per dl_conv_wgrad_multi launch (their pointers travel as kernel arguments) */
+#define DL_WGRAD_C4_PARTS 512       /* dl_wgrad_desc.splitk of the persistent 7x7 stem / head weight gradient: one partial result per workgroup */
 
 int dl_version(void);
 const char *dl_last_error(void);
@@ -68,9 +69,9 @@ const char *dl_last_error(void);
  *                      instead of conv_dot_*_kernel / conv_d1_kernel / conv_d1g_kernel
  *   DL_CONV_W4X3=1     strict ResnetBlock conv on conv_gemm_w4x3_kernel (opt-in; a measured tie with the default 8-phase strict kernel)
  *   DL_PACK_TILED=0    dl_pack_weights_batch with every image in the chunk-per-thread form
- *   DL_NO_X3_GLDS      (set) strict policy on the register-staged round-1 kernels           -- deepliif_amd/ops.py reads the same variable
- *   DL_NO_WGRAD_C4=1   7x7 stem / head weight gradient on the general kernels               -- deepliif_amd/ops.py reads the same variable
- *   DL_NO_C4_X3        (set) strict 7x7 stem / head on the general strict kernels           -- deepliif_amd/ops.py reads the same variable
+ *   DL_NO_X3_GLDS      (set) strict policy on the register-staged round-1 kernels           -- deepliif_amd/ops.py reads the same variable (conv_takes_split)
+ *   DL_NO_WGRAD_C4=1   7x7 stem / head weight gradient on the general kernels
+ *   DL_NO_C4_X3        (set) strict 7x7 stem / head on the general strict kernels
  * dl_switches_reload() re-reads the nine variables (tests that flip one inside a process); NOT thread-safe against concurrent launches.
  * ---------------------------------------------------------------------------------------------------------- */
 int dl_switch_count(void);
@@ -222,6 +223,22 @@ int dl_wgrad_reduce_batch(const dl_wgrad_reduce_entry *table_dev, int count, int
  *                        bit-identical to dl_conv_wgrad with the same splitk.
  * Replaces the per-layer ATen conv backward-weight calls reached from DeepLIIF_model.py:332,429 (networks.py:467-513 for the dominant shape). */
 int dl_wgrad_plan(const dl_wgrad_desc *d, int32_t *tiles, int32_t *ksteps, const char **name);
+
+/* Everything a caller may ask about the kernel of a descriptor, in one call.  wgrad_route() in csrc/wgrad.hip is the ONE place that chooses among the
+ * weight-gradient kernels: the launching entry points run what it says, and dl_wgrad_plan, dl_conv_wgrad_deferrable and this function report it -- a caller
+ * never restates a kernel's conditions.  Pass splitk = 1 to plan a launch (as for dl_wgrad_plan).  Returns 0, < 0 on error (p_split / q_split on a
+ * descriptor whose kernel cannot read split copies; *info is filled all the same). */
+typedef struct dl_wgrad_route {
+    const char *name;        /* as dl_wgrad_plan (static string) */
+    int32_t tiles, ksteps;   /* as dl_wgrad_plan */
+    int32_t batched;         /* dl_wgrad_plan's return value: dl_conv_wgrad_multi takes the kernel */
+    int32_t deferrable;      /* dl_conv_wgrad_deferrable(d) */
+    int32_t takes_split;     /* 1: a strict direct-to-LDS kernel (wgrad_glds_x3_kernel) serves the shape -- an operand without a staged activation may be handed
+                                over as its split copy (p_split / q_split) */
+    int32_t fixed_splitk;    /* != 0: d is a 7x7 stem / head whose persistent kernel partitions its own work; dl_conv_wgrad takes that kernel only with
+                                splitk == fixed_splitk (DL_WGRAD_C4_PARTS), any other split-K runs the general path.  0: the caller sizes split-K */
+} dl_wgrad_route;
+int dl_wgrad_route_info(const dl_wgrad_desc *d, dl_wgrad_route *info);
 int dl_conv_wgrad_multi(const dl_wgrad_desc *d, int n, const void *const *P, const void *const *Q, float *const *grad, float *slab,
                         dl_wgrad_reduce_entry *entries_host, void *stream);
 

@@ -74,12 +74,13 @@ def test_shipped_library_has_no_result_changing_switches(half):
 
 def test_ctypes_struct_sizes_match_the_header(tmp_path):
     c = tmp_path / 'sz.c'
-    c.write_text('#include "%s"\n#include <stdio.h>\nint main(){printf("%%zu %%zu %%zu %%zu %%zu\\n", sizeof(dl_conv_desc), sizeof(dl_wgrad_desc), '
-                 'sizeof(dl_pack_desc), sizeof(dl_norm_desc), sizeof(dl_wgrad_reduce_entry));return 0;}\n' % HEADER)
+    c.write_text('#include "%s"\n#include <stdio.h>\nint main(){printf("%%zu %%zu %%zu %%zu %%zu %%zu\\n", sizeof(dl_conv_desc), sizeof(dl_wgrad_desc), '
+                 'sizeof(dl_pack_desc), sizeof(dl_norm_desc), sizeof(dl_wgrad_reduce_entry), sizeof(dl_wgrad_route));return 0;}\n' % HEADER)
     exe = tmp_path / 'sz'
     subprocess.run(['gcc', str(c), '-o', str(exe)], check=True)
     sizes = [int(v) for v in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split()]
-    assert sizes == [ctypes.sizeof(L.ConvDesc), ctypes.sizeof(L.WgradDesc), ctypes.sizeof(L.PackDesc), ctypes.sizeof(L.NormDesc), ctypes.sizeof(L.WgradReduceEntry)]
+    assert sizes == [ctypes.sizeof(L.ConvDesc), ctypes.sizeof(L.WgradDesc), ctypes.sizeof(L.PackDesc), ctypes.sizeof(L.NormDesc), ctypes.sizeof(L.WgradReduceEntry),
+                     ctypes.sizeof(L.WgradRoute)]
 
 
 def test_product_has_no_cpu_fallback():

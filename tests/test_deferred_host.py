@@ -40,7 +40,7 @@ class StubLib:
         return 0
 
     # round 5: the kernel plan and the batched launch.  The stub calls a layer "batchable" when it has 128-pixel rows and 128-multiple channel counts,
-    # i.e. when geometry.wgrad_batch_shape() also says yes
+    # i.e. the shapes the library's wgrad_w4_kernel serves
     def dl_wgrad_plan(self, d, tiles, ksteps, name):
         d = d._obj
         big = d.Wp == 128 and d.CAp % 128 == 0 and d.CBp % 128 == 0
@@ -48,6 +48,14 @@ class StubLib:
         ksteps._obj.value = d.N * d.Hp if big else max(1, d.N * d.Hp * d.Wp // 32)
         name._obj.value = b'wgrad_w4_kernel' if big else b'wgrad_kernel'
         return 1 if big else 0
+
+    def dl_wgrad_route_info(self, d, info):              # the same answers in one record (what conv_wgrad asks)
+        tiles, ksteps, name = L.i32(), L.i32(), C.c_char_p()
+        r = info._obj
+        r.batched = self.dl_wgrad_plan(d, C.byref(tiles), C.byref(ksteps), C.byref(name))
+        r.name, r.tiles, r.ksteps = name.value, tiles.value, ksteps.value
+        r.deferrable, r.takes_split, r.fixed_splitk = 1, 0, 0
+        return 0
 
     def dl_conv_wgrad_multi(self, d, n, P, Q, grad, slab, entries, stream):
         d = d._obj

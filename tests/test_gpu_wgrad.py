@@ -21,7 +21,7 @@ import wgrad_cases as WC
 import wgrad_ref as WR
 from deepliif_amd import _lib as L
 from deepliif_amd import ops
-from deepliif_amd.geometry import WGRAD_C4_PARTS
+from deepliif_amd._lib import WGRAD_C4_PARTS
 
 from test_gpu_kernels import DEV, DRY, _split_copy, hip, sync
 

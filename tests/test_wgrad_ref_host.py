@@ -31,7 +31,7 @@ import torch
 import wgrad_cases as WC
 import wgrad_ref as WR
 from deepliif_amd import _lib as L
-from deepliif_amd.geometry import WGRAD_C4_PARTS
+from deepliif_amd._lib import WGRAD_C4_PARTS
 
 _CACHE = {}
 

@@ -242,10 +242,8 @@ def effective_splitk(row, policy, splitk, P, Q):
         return splitk
     if row.kernel in ('wgrad_c4', 'wgrad_w4_kernel'):
         return 1
-    d = descriptor_of(row)
-    kw = 1 if d.stack_kw else d.k
-    fast = row.kernel != 'wgrad_kernel'
-    return choose_wgrad_splitk(P.shape[3], d.k * kw * Q.shape[3], P.shape[0] * P.shape[1] * P.shape[2], fast)
+    _, tiles, ksteps, name = plan(L.load(), wgrad_desc(row, policy, 1, P.shape, Q.shape))
+    return choose_wgrad_splitk(name, tiles, ksteps, P.shape[0] * P.shape[1] * P.shape[2])
 
 
 def ranges(ptot, splitk, round_to):
