@@ -410,6 +410,19 @@ class FakeBackend:
         bc1, bc2 = 1 - b1 ** step, 1 - b2 ** step
         p.addcdiv_(m, (v.sqrt() / bc2 ** 0.5).add_(eps), value=-lr / bc1)
 
+    def adam_hyper(self, lr, b1, b2, eps, step, gscale, hyper_host):
+        """the slots dl_adam_hyper documents: lr, beta1, beta2, eps, 1 - beta1^t, sqrt(1 - beta2^t), grad_scale, 0.  The step itself is not among them and
+        adam_step takes the step, so the emulation remembers it for adam_step_dev"""
+        self._hyper_step = step
+        hyper_host[:8] = torch.tensor([lr, b1, b2, eps, 1 - b1 ** step, (1 - b2 ** step) ** 0.5, gscale, 0.0], dtype=torch.float64).float()
+
+    def adam_step_dev(self, p, g, m, v, hyper_dev):
+        """adam_step with the scalars read back from the hyper tensor's slots (fp32, as the kernel reads them); the bias corrections in slots 4 and 5 must be
+        the ones of the remembered step"""
+        lr, b1, b2, eps, bc1, bc2_sqrt, gscale = (float(h) for h in hyper_dev[:7].cpu())
+        step = self._hyper_step
+        assert abs(bc1 - (1 - b1 ** step)) <= 1e-6 and abs(bc2_sqrt - (1 - b2 ** step) ** 0.5) <= 1e-6 and float(hyper_dev[7]) == 0.0
+        self.adam_step(p, g, m, v, lr, b1, b2, eps, step, gscale)
 
     # ---- tiles (include/deepliif_hip.h dl_tile_*): written from the header's formulas, not from the oracle
     @staticmethod
