@@ -108,6 +108,13 @@ SIGNATURES = {
     'dl_pp_render_paint': (_i, [_i, _vp, _i64, _vp, _i, _vp, _i, _i, _i, _i, _vp, _vp]),
     'dl_pp_render_ws_bytes': (C.c_size_t, [_i, _i]),
     'dl_pp_render_finish': (_i, [_vp, C.c_size_t, _vp, _vp, _i, _vp, _i, _i, _vp, C.c_size_t, _vp, C.c_size_t, _vp]),
+    'dl_stat_similarity_ws_bytes': (C.c_size_t, [_i, _i, _i]),
+    'dl_stat_similarity': (_i, [_vp, C.c_size_t, C.c_size_t, _vp, C.c_size_t, C.c_size_t, _i, _i, _i, _i, C.c_double, _vp, _vp, _vp]),
+    'dl_stat_confusion': (_i, [_vp, C.c_size_t, C.c_size_t, _vp, C.c_size_t, C.c_size_t, _i, _i, _i, _vp, _vp]),
+    'dl_stat_label_ws_bytes': (C.c_size_t, [_i, _i]),
+    'dl_stat_label': (_i, [_vp, C.c_size_t, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    'dl_stat_aji_ws_bytes': (C.c_size_t, [_i, _i]),
+    'dl_stat_aji': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp]),
     'dl_conv_forward_bnstats': (_i, [C.POINTER(ConvDesc), _vp, _vp, _vp, _vp, _vp, C.POINTER(ConvBnStats), _vp]),
     'dl_conv_kernel_name': (C.c_char_p, [C.POINTER(ConvDesc)]),
     'dl_conv_add_supported': (_i, [C.POINTER(ConvDesc)]),

@@ -682,6 +682,39 @@ size_t dl_pp_render_ws_bytes(int H, int W);
 int dl_pp_render_finish(const void *orig, size_t orig_row_stride, const int *owner, const int *rows, int n, void *ws, int H, int W,
                         void *overlay, size_t overlay_row_stride, void *refined, size_t refined_row_stride, void *stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * Evaluation metrics (DeepLIIF_Statistics/ComputeStatistics.py: compute_mse_ssim_scores :72-92, compute_IHC_scoring :150-182;
+ * Segmentation_Metrics.py: compute_metrics_gpu :13-39, compute_aji :64-102).  uint8 images with strides in bytes; the integer results are exact,
+ * the two floating-point ones are computed in double in a fixed order (no floating-point atomics): two runs give the same bits.
+ *
+ * dl_stat_similarity: N image pairs (a[n], b[n]), channels = 3 (RGB, pixel stride 3) or 1 (gray, pixel stride 1), H, W >= 11 ->
+ *   out double [N][2] (device) = {mse, ssim}.  Gray value Y = 0.2125 R/255 + 0.7154 G/255 + 0.0721 B/255 (skimage rgb2gray) or v/255;
+ *   mse = mean (Ya - Yb)^2; ssim = skimage structural_similarity(gaussian_weights=True, sigma=1.5, use_sample_covariance=False,
+ *   data_range): 11-tap normalised Gaussian applied separably to x, y, xx, yy, xy, C1 = (0.01 R)^2, C2 = (0.03 R)^2, the mean of S over
+ *   [5:H-5, 5:W-5].  ws = dl_stat_similarity_ws_bytes(N, H, W) bytes (per-workgroup partial sums; 0 = empty or too large problem).
+ * dl_stat_confusion: N pairs of RGB images (prediction, ground truth) -> out int64 [N][2][4] (device) = {TP, FP, FN, TN} of "> 0";
+ *   [.][0] is channel 0 (positive cells), [.][1] is channel 2 (negative cells).  TP + FN is the number of non-zero ground-truth pixels.
+ * dl_stat_label: skimage.measure.label(plane, background=0) of one uint8 channel (plane[y * row_stride + x * pixel_stride]) after values
+ *   below min_value are set to 0 (and, with binarize != 0, the others to 1: a "> 0" mask): 8-connected components of EQUAL non-zero value, numbered 1 .. n in raster order of their first pixel ->
+ *   labels int32 [H][W] (0 = background), info int32 [2] = {n, labelled pixels}, sizes int32 [H * W] of which the first n are written
+ *   (sizes[i] = pixels of component i + 1); all on the device.  ws = dl_stat_label_ws_bytes(H, W) bytes.
+ * dl_stat_aji: two outputs of dl_stat_label (ground truth and prediction, same H x W) -> out int64 [3] (device) = {total_intersection,
+ *   total_union, total_U} of compute_aji: the ground-truth components in label order each take the still-unmarked predicted component
+ *   with the largest intersection (the smallest label among equals) and add the intersection and the union; one without any adds nothing;
+ *   total_U = pixels of the predicted components left unmarked.  ws = dl_stat_aji_ws_bytes(H, W) bytes.
+ * ---------------------------------------------------------------------------------------------------------- */
+size_t dl_stat_similarity_ws_bytes(int N, int H, int W);
+int dl_stat_similarity(const void *a, size_t a_row_stride, size_t a_image_stride, const void *b, size_t b_row_stride, size_t b_image_stride,
+                       int channels, int N, int H, int W, double data_range, void *ws, double *out, void *stream);
+int dl_stat_confusion(const void *pred, size_t pred_row_stride, size_t pred_image_stride, const void *gt, size_t gt_row_stride,
+                      size_t gt_image_stride, int N, int H, int W, long long *out, void *stream);
+size_t dl_stat_label_ws_bytes(int H, int W);
+int dl_stat_label(const void *plane, size_t row_stride, int pixel_stride, int H, int W, int min_value, int binarize, void *ws, int *labels,
+                  int *info, int *sizes, void *stream);
+size_t dl_stat_aji_ws_bytes(int H, int W);
+int dl_stat_aji(const int *gt_labels, const int *gt_info, const int *gt_sizes, const int *pred_labels, const int *pred_info,
+                const int *pred_sizes, int H, int W, void *ws, long long *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
