@@ -115,6 +115,14 @@ SIGNATURES = {
     'dl_stat_label': (_i, [_vp, C.c_size_t, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     'dl_stat_aji_ws_bytes': (C.c_size_t, [_i, _i]),
     'dl_stat_aji': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp]),
+    'dl_swd_patches_ws_bytes': (C.c_size_t, [_i, _i, _i, _i]),
+    'dl_swd_patches': (_i, [_vp, C.c_size_t, C.c_size_t, _i, _i, _i, _i, _vp, C.POINTER(C.c_int), C.c_longlong, C.c_longlong, _vp, _vp, _vp]),
+    'dl_swd_normalise_ws_bytes': (C.c_size_t, [C.c_longlong]),
+    'dl_swd_normalise': (_i, [_vp, C.c_longlong, _vp, _vp, _vp]),
+    'dl_swd_lds_rows': (_i, []),
+    'dl_swd_route': (_i, [C.c_longlong, _i, _i]),
+    'dl_swd_distance_ws_bytes': (C.c_size_t, [C.c_longlong, _i, _i]),
+    'dl_swd_distance': (_i, [_vp, _vp, C.c_longlong, _vp, _i, _i, _vp, _vp, _vp]),
     'dl_conv_forward_bnstats': (_i, [C.POINTER(ConvDesc), _vp, _vp, _vp, _vp, _vp, C.POINTER(ConvBnStats), _vp]),
     'dl_conv_kernel_name': (C.c_char_p, [C.POINTER(ConvDesc)]),
     'dl_conv_add_supported': (_i, [C.POINTER(ConvDesc)]),

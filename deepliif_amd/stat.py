@@ -5,11 +5,12 @@
                                                                             (compute_segmentation_metrics, Segmentation_Metrics.py:105-232)
   aji                     the aggregated Jaccard index                      (compute_aji, Segmentation_Metrics.py:64-102)
   ihc_score_diff          difference of the positive-cell fractions         (compute_IHC_scoring, ComputeStatistics.py:150-182)
+  swd, compute_swd        the sliced Wasserstein distance of two image sets (swd.py; the <type>_swd_value column, ComputeStatistics.py:116-128)
   compute_statistics      the directory driver that writes the script's CSV files
   get_cell_count_metrics  metrics.json for --with-val training              (deepliif/stat/__init__.py)
 
-The per-pixel work runs in csrc/stat.hip (dl_stat_similarity, dl_stat_confusion, dl_stat_label, dl_stat_aji); no label image and no per-pixel
-array comes back to the host, only a few numbers per image.  Images are PIL images, ndarrays or CUDA tensors, uint8: H x W x 3 (RGB), H x W
+The per-pixel work runs in csrc/stat.hip (dl_stat_similarity, dl_stat_confusion, dl_stat_label, dl_stat_aji) and csrc/swd.hip (dl_swd_patches,
+dl_swd_normalise, dl_swd_distance); no label image and no per-pixel array comes back to the host, only a few numbers per image.  Images are PIL images, ndarrays or CUDA tensors, uint8: H x W x 3 (RGB), H x W
 (gray), a list of them, or one [N, H, W, 3] array.  The images of a pair must have the same size: the reference scripts cv2.resize to 512 x 512,
 this module raises instead.  There is no CPU fallback: without the HIP library (or with CPU tensors that cannot be uploaded) this module raises.
 """
@@ -312,6 +313,169 @@ def ihc_score_diff(gt, pred):
     return {'diff': np.array(diffs, dtype=np.float64), 'mean': sum(diffs) / len(diffs)}
 
 
+# ---------------------------------------------------------------------------------------------------- sliced Wasserstein distance
+SWD_PATCH = 7                # swd.py hard-codes the 6 = 7 - 1 of the window count and the 3 * 7 * 7 of the descriptor
+SWD_COLUMNS = 3 * SWD_PATCH * SWD_PATCH
+SWD_CHUNK = 16               # images whose pyramid is held at once: the pyramid workspace does not grow with the set
+
+
+def swd_level_shapes(H, W, n_pyramids):
+    """(h, w) of the n_pyramids + 1 levels: pyramid_down gives floor((h - 1) / 2) + 1"""
+    shapes = [(int(H), int(W))]
+    for _ in range(int(n_pyramids)):
+        h, w = shapes[-1]
+        shapes.append(((h - 1) // 2 + 1, (w - 1) // 2 + 1))
+    return shapes
+
+
+class SwdDraws:
+    """The random draws of one swd() call: per level the patch positions (int64 ndarray, at most n_descriptors of them) and the projection
+    directions (float32 ndarray [n_repeat_projection][147][proj_per_repeat], every column divided by its unbiased std)."""
+
+    def __init__(self, level_shapes, n_descriptors, n_repeat_projection, proj_per_repeat, indices, projections):
+        self.level_shapes = [tuple(int(v) for v in s) for s in level_shapes]
+        self.n_descriptors, self.n_repeat_projection, self.proj_per_repeat = int(n_descriptors), int(n_repeat_projection), int(proj_per_repeat)
+        self.indices, self.projections = indices, projections
+
+
+def swd_draws(level_shapes, n_descriptors=128, n_repeat_projection=128, proj_per_repeat=4, generator=None) -> SwdDraws:
+    """The draws of swd.py:115-133, on the host, in the reference's order: per level torch.randperm((h - 6) * (w - 6))[:n_descriptors], then
+    n_repeat_projection times torch.randn(147, proj_per_repeat) divided by its columns' unbiased std, in float32.  generator=None draws from
+    torch's global CPU generator, so after torch.manual_seed(s) these are the draws of the reference's swd(..., device='cpu') after the same
+    call.  Needs neither the GPU nor the HIP library."""
+    if n_descriptors < 1 or n_repeat_projection < 1 or proj_per_repeat < 2:
+        raise ValueError('n_descriptors, n_repeat_projection >= 1 and proj_per_repeat >= 2 (the unbiased std of one value does not exist)')
+    indices, projections = [], []
+    for h, w in level_shapes:
+        if h < SWD_PATCH or w < SWD_PATCH:
+            raise ValueError(f'a level of {h} x {w} is below the {SWD_PATCH} x {SWD_PATCH} patch')
+        n = (int(h) - (SWD_PATCH - 1)) * (int(w) - (SWD_PATCH - 1))
+        indices.append(torch.randperm(n, generator=generator)[:n_descriptors].numpy().astype(np.int64))
+        mats = []
+        for _ in range(n_repeat_projection):
+            r = torch.randn(SWD_COLUMNS, proj_per_repeat, generator=generator)
+            mats.append((r / torch.std(r, dim=0, keepdim=True)).numpy())
+        projections.append(np.stack(mats).astype(np.float32))
+    return SwdDraws(level_shapes, n_descriptors, n_repeat_projection, proj_per_repeat, indices, projections)
+
+
+def _swd_patches(t: torch.Tensor, n_pyramids: int, indices) -> list:
+    """stage 1 (dl_swd_patches): a _batch RGB tensor -> per level the RAW patch matrix, float64 [N * D_l][147] on the device"""
+    lib = _lib()
+    N, H, W, _ = (int(v) for v in t.shape)
+    counts = [int(len(i)) for i in indices]
+    idx = torch.from_numpy(np.concatenate([np.asarray(i) for i in indices]).astype(np.int32)).to(t.device)
+    out = torch.empty(N * sum(counts) * SWD_COLUMNS, dtype=torch.float64, device=t.device)
+    chunk = min(N, SWD_CHUNK)
+    nbytes = int(lib.dl_swd_patches_ws_bytes(chunk, H, W, n_pyramids))
+    if nbytes == 0:
+        raise RuntimeError(f'dl_swd_patches_ws_bytes refused N={chunk} H={H} W={W} n_pyramids={n_pyramids}')
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=t.device)
+    c_counts = (L.C.c_int * len(counts))(*counts)
+    p = ops._ptr
+    for n0 in range(0, N, chunk):
+        n = min(chunk, N - n0)
+        L.check(lib.dl_swd_patches(p(t[n0:]), t.stride(1), t.stride(0), n, H, W, n_pyramids, p(idx), c_counts, N, n0, p(ws), p(out), ops._stream(t)),
+                'dl_swd_patches', lib)
+    mats, off = [], 0
+    for d in counts:
+        mats.append(out[off:off + N * d * SWD_COLUMNS].view(N * d, SWD_COLUMNS))
+        off += N * d * SWD_COLUMNS
+    return mats
+
+
+def _swd_normalise(x: torch.Tensor) -> torch.Tensor:
+    """stage 2 (dl_swd_normalise): x float64 [R][147] is normalised in place -> stats float64 [6] = mean, unbiased std per channel (device)"""
+    lib = _lib()
+    R = int(x.shape[0])
+    ws = torch.empty(int(lib.dl_swd_normalise_ws_bytes(R)), dtype=torch.uint8, device=x.device)
+    stats = torch.empty(6, dtype=torch.float64, device=x.device)
+    L.check(lib.dl_swd_normalise(ops._ptr(x), R, ops._ptr(ws), ops._ptr(stats), ops._stream(x)), 'dl_swd_normalise', lib)
+    return stats
+
+
+def _swd_distances(a: torch.Tensor, b: torch.Tensor, proj: torch.Tensor, route: int = 0) -> torch.Tensor:
+    """stage 3 (dl_swd_distance): normalised sets a, b float64 [R][147], directions proj float32 [P][147] -> float64 [P] (device)"""
+    lib = _lib()
+    R, P = int(a.shape[0]), int(proj.shape[0])
+    nbytes = int(lib.dl_swd_distance_ws_bytes(R, P, int(route)))
+    ws = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=a.device)
+    out = torch.empty(P, dtype=torch.float64, device=a.device)
+    L.check(lib.dl_swd_distance(ops._ptr(a), ops._ptr(b), R, ops._ptr(proj), P, int(route), ops._ptr(ws), ops._ptr(out), ops._stream(a)),
+            'dl_swd_distance', lib)
+    return out
+
+
+def swd_lds_rows() -> int:
+    """the most rows (images x descriptors) whose projections a workgroup sorts in LDS; above, hipcub sorts them in global memory"""
+    return int(_lib().dl_swd_lds_rows())
+
+
+def _swd_directions(projections: np.ndarray, device) -> torch.Tensor:
+    """[n_repeat][147][proj_per_repeat] -> float32 [n_repeat * proj_per_repeat][147] on the device"""
+    return torch.from_numpy(np.ascontiguousarray(projections.transpose(0, 2, 1).reshape(-1, SWD_COLUMNS), dtype=np.float32)).to(device)
+
+
+def swd(gt, pred, n_pyramids=None, slice_size=7, n_descriptors=128, n_repeat_projection=128, proj_per_repeat=4, return_by_resolution=False,
+        generator=None, draws=None, route=0):
+    """The sliced Wasserstein distance of two image SETS, swd() of DeepLIIF_Statistics/swd.py -> float, or with return_by_resolution a float64
+    ndarray [n_pyramids + 1] (finest level first).
+
+    Images as image_similarity takes them, RGB only, both sets of one shape.  Per level of a Laplacian pyramid (5 x 5 binomial kernel, zero
+    padding, nearest up-sampling; n_pyramids defaults to round(log2(H // 16))) the same n_descriptors random 7 x 7 x 3 patches are taken from
+    every image of both sets (all positions where a level has fewer), normalised per channel with the mean and unbiased std of their own set,
+    projected onto n_repeat_projection x proj_per_repeat random directions and sorted; the level's value is the mean absolute difference of
+    the sorted projections, the result the levels' mean times 1e3.  It needs no network weights.
+
+    The random draws are made on the host by swd_draws (generator=None: torch's global CPU generator, as the reference with device='cpu'),
+    or passed as draws= to reuse them.  Everything else runs on the GPU in float64 in a fixed order: with the same draws two calls return
+    the same bits, and swd(x, x) is exactly 0.  The reference computes in float32, so its numbers agree to about 1e-6 relative, not
+    bit for bit.  route: 0 chooses the sort by size, 1 / 2 force the LDS / global-memory sort (dl_swd_distance)."""
+    if slice_size != SWD_PATCH:
+        raise ValueError(f'slice_size={slice_size}: the reference hard-codes 7 (the 6 of its window count and the 3 * 7 * 7 of its projections)')
+    a, b = _pair(gt, pred)
+    if a.shape[3] != 3:
+        raise ValueError('expected RGB images, got gray ones')
+    N, H, W, _ = (int(v) for v in a.shape)
+    if n_pyramids is None:
+        if H < 16:
+            raise ValueError(f'n_pyramids defaults to round(log2(H // 16)), which does not exist for H={H}: pass n_pyramids')
+        n_pyramids = int(np.rint(np.log2(H // 16)))
+    n_pyramids = int(n_pyramids)
+    if n_pyramids < 0 or n_pyramids > 15:
+        raise ValueError(f'n_pyramids={n_pyramids}')
+    if H % (1 << n_pyramids) or W % (1 << n_pyramids):
+        raise ValueError(f'H={H} and W={W} must be divisible by 2**n_pyramids = {1 << n_pyramids} (the reference fails there with a shape mismatch)')
+    shapes = swd_level_shapes(H, W, n_pyramids)
+    if shapes[-1][0] < SWD_PATCH or shapes[-1][1] < SWD_PATCH:
+        raise ValueError(f'the smallest level, {shapes[-1][0]} x {shapes[-1][1]}, is below the 7 x 7 patch: fewer pyramids or larger images')
+    if draws is None:
+        draws = swd_draws(shapes, n_descriptors, n_repeat_projection, proj_per_repeat, generator)
+    elif draws.level_shapes != shapes:
+        raise ValueError(f'draws were made for the levels {draws.level_shapes}, the images have {shapes}')
+    pa, pb = _swd_patches(a, n_pyramids, draws.indices), _swd_patches(b, n_pyramids, draws.indices)
+    per_column = []
+    for l in range(n_pyramids + 1):
+        _swd_normalise(pa[l])
+        _swd_normalise(pb[l])
+        per_column.append(_swd_distances(pa[l], pb[l], _swd_directions(draws.projections[l], a.device), route))
+    cols = torch.stack(per_column).cpu().numpy()                               # one device-to-host copy: [levels][n_repeat * proj_per_repeat]
+    levels = np.array([row.reshape(draws.n_repeat_projection, draws.proj_per_repeat).mean(axis=1).mean() for row in cols], dtype=np.float64) * 1e3
+    return levels if return_by_resolution else float(levels.mean())
+
+
+_swd = swd                   # (compute_statistics has a flag of that name)
+
+
+def compute_swd(orig_images, mask_images, device=None):
+    """compute_swd of swd.py:153-158: two [N, H, W, 3] uint8 arrays -> swd() with the defaults.  device (the reference's 'cpu' / 'cuda') only
+    says where the tensors are put: a torch.device or None for the current GPU."""
+    if device is not None and torch.device(device).type == 'cuda':
+        orig_images, mask_images = (x.to(device) if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x)).to(device)
+                                    for x in (orig_images, mask_images))
+    return swd(orig_images, mask_images)
+
+
 # ---------------------------------------------------------------------------------------------------- the directory driver
 def _read(path):
     from PIL import Image
@@ -342,13 +506,13 @@ def _write_rows(path, rows, columns):
 
 
 def compute_statistics(gt_path, model_path, output_path, model_name='DeepLIIF', mode='Segmentation', image_types=('Hema', 'DAPI', 'Lap2', 'Marker'),
-                       aji=False, raw_segmentation=False):
+                       aji=False, raw_segmentation=False, swd=False):
     """DeepLIIF_Statistics/ComputeStatistics.py on two directories of PNG files -> the dict the script calls all_info; writes into output_path:
 
       mode 'Segmentation':   segmentation_info_<mode>_<model>_100_50.csv (Model, image_name, cell_type, precision, recall, f1, Dice, IOU, PixAcc
                              [, AJI]), IHC_Scoring_info_<mode>_<model>.csv (Model, Sample, Diff_IHC_Score)
       mode 'ImageSynthesis': metrics_<mode>_<model>.csv (Model, <type>_MSE_avg, <type>_MSE_std, <type>_ssim_avg, <type>_ssim_std per image type;
-                             the script computes these in this mode and writes nothing)
+                             and with swd=True <type>_swd_value after them; the script computes these in this mode and writes nothing)
       mode 'All':            all three, the metrics file with the segmentation means (precision, precision_positive, ...) after the similarity columns.
 
     Files are paired by name as the script pairs them: every `<name>_SegRefined.png` of model_path with `<name>.png` of gt_path; every file of
@@ -357,9 +521,13 @@ def compute_statistics(gt_path, model_path, output_path, model_name='DeepLIIF', 
     partner are skipped, where the script would stop).  Directory listings are sorted.  Pairs of one size go through the kernels as one batch;
     the images of a pair must have the same size (the script resizes to 512 x 512, this does not).
 
-    Left out: the FID, inception-score and SWD columns (they need Inception weights and TensorFlow, which this package does not ship) and
-    raw_segmentation=True (the `_Seg.png` route through positive_negative_masks): it raises NotImplementedError.  SSIM uses data_range=1.0 and
-    the 2-D definition (see image_similarity)."""
+    swd=True adds the script's <type>_swd_value column (compute_swd, ComputeStatistics.py:116-128): ONE sliced Wasserstein distance per image
+    type over all pairs of that type (see swd(); the draws come from torch's global CPU generator, so seed it for a repeatable value).  It is a
+    distance of two sets, so the pairs of a type must all have one size.  The default leaves every file as it is without it.
+
+    Left out: the FID and inception-score columns (they need Inception weights and TensorFlow, which this package does not ship; SWD needs
+    neither) and raw_segmentation=True (the `_Seg.png` route through positive_negative_masks): it raises NotImplementedError.  SSIM uses
+    data_range=1.0 and the 2-D definition (see image_similarity)."""
     if raw_segmentation:
         raise NotImplementedError('raw_segmentation=True (positive_negative_masks on *_Seg.png) is not implemented; evaluate the *_SegRefined.png images')
     if mode not in ('Segmentation', 'ImageSynthesis', 'All'):
@@ -380,6 +548,12 @@ def compute_statistics(gt_path, model_path, output_path, model_name='DeepLIIF', 
                 mse[idx], ssim[idx] = r['mse'], r['ssim']
             all_info[img_type + '_MSE_avg'], all_info[img_type + '_MSE_std'] = np.mean(mse), np.std(mse)
             all_info[img_type + '_ssim_avg'], all_info[img_type + '_ssim_std'] = np.mean(ssim), np.std(ssim)
+            if swd:
+                if len(_by_shape(preds)) != 1:
+                    raise ValueError(f'swd=True: the {img_type} images have the sizes {sorted(set(x.shape for x in preds))}; the sliced Wasserstein '
+                                     f'distance is taken over one set of one size (the script resizes to 512 x 512, this does not)')
+                rgb = lambda x: x if x.ndim == 3 else np.repeat(x[:, :, None], 3, axis=2)          # (the script's cv2.imread gives three channels)
+                all_info[img_type + '_swd_value'] = _swd([rgb(x) for x in gts], [rgb(x) for x in preds])
 
     if mode in ('Segmentation', 'All'):
         postfix = '_SegRefined.png'

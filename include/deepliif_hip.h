@@ -715,6 +715,40 @@ size_t dl_stat_aji_ws_bytes(int H, int W);
 int dl_stat_aji(const int *gt_labels, const int *gt_info, const int *gt_sizes, const int *pred_labels, const int *pred_info,
                 const int *pred_sizes, int H, int W, void *ws, long long *out, void *stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * Sliced Wasserstein distance of two image sets (DeepLIIF_Statistics/swd.py), in three stages.  All arithmetic is double in a fixed order
+ * (no floating-point atomics): two runs give the same bits.  The random draws (patch positions, projection directions) are the caller's.
+ *
+ * dl_swd_patches: a chunk of N uint8 RGB images (pixel stride 3, strides in bytes; images n0 .. n0 + N - 1 of a set of n_total) -> the RAW
+ *   7 x 7 x 3 patches of every Laplacian-pyramid level.  Level 0 is v / 255; level l + 1 is the 5 x 5 kernel outer([1 4 6 4 1]) / 256 at
+ *   stride 2 with zero padding 2 (evaluated rows first); Laplacian level l < n_pyramids is g_l - conv5x5(nearest_upsample_x2(g_(l+1))) with
+ *   zero padding, the last level is g_n itself.  H and W must be divisible by 2^n_pyramids and the smallest level at least 7 x 7.
+ *   indices: device int32, the levels' position lists one after the other, counts[l] (HOST int [n_pyramids + 1]) of them at level l;
+ *   position i is the window at row i / (w_l - 6), column i % (w_l - 6); the same positions serve every image.  out (device double):
+ *   level l's matrix [n_total * counts[l]][147] begins 147 * n_total * (counts[0] + ... + counts[l-1]) values in; row = image * counts[l] +
+ *   descriptor, column = channel * 49 + dy * 7 + dx; this call writes the rows of its N images.  Only the chosen patches are evaluated.
+ *   ws = dl_swd_patches_ws_bytes(N, H, W, n_pyramids) bytes (levels 1 .. n of the chunk; 0 = refused): it grows with the chunk, not the set.
+ * dl_swd_normalise: x double [R][147] of ONE set -> stats double [6] (device) = mean and unbiased std per channel over all rows and the 49
+ *   columns of the channel (two passes: the mean, then the squared deviations), and x = (x - mean) / (std + 1e-8) in place.
+ *   ws = dl_swd_normalise_ws_bytes(R) bytes.
+ * dl_swd_distance: two normalised sets a, b double [R][147] and P directions proj float [P][147] -> out double [P] (device):
+ *   out[p] = mean_i |sort(a proj_p)_i - sort(b proj_p)_i|.  One pass projects both sets onto a tile of 32 directions per workgroup (each
+ *   row is loaded once per tile) into the workspace as [2 P][R]; a bounded number of directions per pass.  Then route 1, the LDS route: one
+ *   workgroup per direction takes both projections into LDS, pads to a power of two with +inf, runs a bitonic network and sums |a - b| in a
+ *   fixed tree; R <= dl_swd_lds_rows() (both sets at 8 bytes per value within the CU's 160 KiB), else the call is refused with -1.  Route 2,
+ *   the large route: hipcub's segmented radix sort and a reduce kernel.  route 0 chooses by size, 1 / 2 force.  dl_swd_route -> the route a
+ *   call would take (1 | 2, 0 = refused).  ws = dl_swd_distance_ws_bytes(R, P, route) bytes (0 = refused).
+ * ---------------------------------------------------------------------------------------------------------- */
+size_t dl_swd_patches_ws_bytes(int N, int H, int W, int n_pyramids);
+int dl_swd_patches(const void *images, size_t row_stride, size_t image_stride, int N, int H, int W, int n_pyramids, const int *indices,
+                   const int *counts, long long n_total, long long n0, void *ws, double *out, void *stream);
+size_t dl_swd_normalise_ws_bytes(long long R);
+int dl_swd_normalise(double *x, long long R, void *ws, double *stats, void *stream);
+int dl_swd_lds_rows(void);
+int dl_swd_route(long long R, int P, int route);
+size_t dl_swd_distance_ws_bytes(long long R, int P, int route);
+int dl_swd_distance(const double *a, const double *b, long long R, const float *proj, int P, int route, void *ws, double *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
