@@ -17,6 +17,12 @@ void dl_set_error(const char *fmt, ...);
 #define DL_FAIL(...) do { dl_set_error(__VA_ARGS__); return -1; } while (0)
 #define DL_CHECK_LAUNCH(name) do { hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) { \
     dl_set_error("%s: launch failed: %s", name, hipGetErrorString(e_)); return -2; } } while (0)
+// The grant every kernel with more than 64 KiB of dynamic LDS needs before its launch (error.cpp): 0 when `kern` may use `bytes` on the calling
+// thread's current device -- the runtime is asked once per (device, kernel) and again only for a larger size; -1 with the error set, naming `who`,
+// when the runtime refuses (nothing is remembered then).  Safe from several threads.
+int dl_lds_limit(const void *kern, size_t bytes, const char *who);
+// an integer as a type: how a generic lambda takes a compile-time constant as an argument (`[&](auto ic) { constexpr int k = decltype(ic)::value; ... }`)
+template <int V> struct IC { static constexpr int value = V; };
 
 // ---- the library's 16-bit format.  The same sources build two libraries (Makefile): libdeepliif_hip.so with bfloat16 (training + inference; the
 // reference's fp32 range, 8 bits of precision) and libdeepliif_hip_f16.so (-DDL_H16_FP16) with IEEE half as the storage AND MFMA operand type: 11 bits of

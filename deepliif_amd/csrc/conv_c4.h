@@ -251,17 +251,8 @@ static void c4_fill_args(C4Args &ca, const ConvArgs &a0, const dl_conv_desc *d) 
     ca.abl = abl_env ? atoi(abl_env) : 0;
 }
 
-// launch with the dynamic-LDS attribute set once per instantiation
 static int c4_launch(void (*kern)(const C4Args), const C4Args &ca, const dl_conv_desc *d, size_t smem, hipStream_t stream, const char *what) {
-    static void (*attr_done[18])(const C4Args) = {};
-    bool seen = false;
-    for (int i = 0; i < 18; ++i) seen |= attr_done[i] == kern;
-    if (!seen) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-        if (e != hipSuccess) DL_FAIL("%s: hipFuncSetAttribute(%zu): %s", what, smem, hipGetErrorString(e));
-        for (int i = 0; i < 18; ++i)
-            if (!attr_done[i]) { attr_done[i] = kern; break; }
-    }
+    if (dl_lds_limit(reinterpret_cast<const void *>(kern), smem, what)) return -1;
     const int ntiles = d->N * ca.tiles_w * ca.tiles_h;
     const int per_y = 512 / (d->Co / 64) > 0 ? 512 / (d->Co / 64) : 1;       // ~2 workgroups per CU in total
     dim3 grid(ntiles < per_y ? ntiles : per_y, d->Co / 64);

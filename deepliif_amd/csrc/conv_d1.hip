@@ -12,12 +12,6 @@
 // Same descriptor and packed weights as the gather GEMM (n_phase = 1, in_step = 2, 16 taps (kh - 1, kw - 1) kh-major): no host change beyond the dispatch.
 #include "conv_args.h"
 
-typedef __attribute__((ext_vector_type(16))) float f32x16_t;
-typedef __attribute__((address_space(3))) char lds_char_t;
-typedef __attribute__((address_space(3))) const bf16x8_t lds_frag_t;
-
-template <int V> struct D1IC { static constexpr int value = V; };
-
 struct D1Args {
     ConvArgs a;
     int R, nstrips;
@@ -77,7 +71,7 @@ __global__ void __launch_bounds__(256, 2) conv_d1_kernel(const D1Args sa) {
         const bool real = r >= 0 && r < a.Hi;
         const __amdgpu_buffer_rsrc_t rs = real ? rsrc_in : rsrc_none;
         const int soff = real ? r * (int)row_bytes : 0;
-        stage_piece(D1IC<0>{}, soff, slot, rs); stage_piece(D1IC<1>{}, soff, slot, rs); stage_piece(D1IC<2>{}, soff, slot, rs);
+        stage_piece(IC<0>{}, soff, slot, rs); stage_piece(IC<1>{}, soff, slot, rs); stage_piece(IC<2>{}, soff, slot, rs);
     };
 
     // ---- fragment address (bytes inside a slot): pixel q = 2 wo + 2p + lh, wo = ph*128 + j*32 + lr   ->   + p*32 + j*1024
@@ -163,14 +157,14 @@ __global__ void __launch_bounds__(256, 2) conv_d1_kernel(const D1Args sa) {
     stage(2 * ho0 + 1, 0);
     stage(2 * ho0 + 2, 1);
     asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
-    row_mac(D1IC<0>{}, D1IC<-1>{}, 2, accA, accB);
-    row_mac(D1IC<1>{}, D1IC<-1>{}, 3, accA, accB);
+    row_mac(IC<0>{}, IC<-1>{}, 2, accA, accB);
+    row_mac(IC<1>{}, IC<-1>{}, 3, accA, accB);
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");            // slots 2, 3 are about to be refilled
     auto out_row = [&](int t, int s0, f32x16_t (&cur)[4], f32x16_t (&nxt)[4]) __attribute__((always_inline)) {
         const int ho = ho0 + t;
         if (t + 1 < R) { stage(2 * ho + 3, s0 ^ 2); stage(2 * ho + 4, (s0 ^ 2) + 1); }
-        row_mac(D1IC<2>{}, D1IC<0>{}, s0, cur, nxt);
-        row_mac(D1IC<3>{}, D1IC<1>{}, s0 + 1, cur, nxt);
+        row_mac(IC<2>{}, IC<0>{}, s0, cur, nxt);
+        row_mac(IC<3>{}, IC<1>{}, s0 + 1, cur, nxt);
         __builtin_amdgcn_sched_barrier(0);          // the row's MFMAs stay in front of the epilogue that reads their accumulators
         epilogue(cur, ho);
         __builtin_amdgcn_sched_barrier(0);
@@ -183,17 +177,7 @@ __global__ void __launch_bounds__(256, 2) conv_d1_kernel(const D1Args sa) {
 }
 
 // strip height: an even divisor of Ho that gives the grid about two workgroups per CU
-static int d1_strip_rows(const ConvArgs &a) {
-    const int per_img = a.N * (a.Co / 64);
-    int best = 0;
-    for (int R = 2; R <= a.Ho; R += 2) {
-        if (a.Ho % R) continue;
-        const int wgs = per_img * (a.Ho / R);
-        if (best == 0 || wgs >= 480) best = R;
-        if (wgs < 480) break;
-    }
-    return best;
-}
+static int d1_strip_rows(const ConvArgs &a) { return strip_rows(a.N * (a.Co / 64), a.Ho, 2, 480); }
 
 // The layer this kernel serves: one phase, input step 2, the sixteen taps (kh - 1, kw - 1) kh-major, zero padding, exactly 8 (padded) contracted channels, output
 // channels a multiple of 64, exact 2x geometry with output rows of exactly 256 pixels, bf16, no split-K / raw accumulators / input activation / fused statistics.
@@ -203,9 +187,9 @@ bool d1_eligible(const ConvArgs &a) {
     if (a.Hi != 2 * a.Ho || a.Wi != 2 * a.Wo || a.Hq != a.Ho || a.Wq != a.Wo || a.Wo != D1_W || (a.Ho & 1)) return false;
     if (a.pad_mode != DL_PAD_ZERO || a.bn_y != nullptr || a.in_act != DL_ACT_NONE || a.epi_old || a.stats_part != nullptr) return false;
     if (a.act != DL_ACT_NONE && a.act != DL_ACT_RELU && a.act != DL_ACT_LRELU) return false;
-    if ((size_t)a.Hi * a.Wi * (size_t)a.in_pstride * 2 >= ((size_t)1 << 31) || (size_t)a.Ho * a.Wo * (size_t)a.out_pstride * 2 >= ((size_t)1 << 31)) return false;
+    if (!conv_fits_i32(a)) return false;
     for (int t = 0; t < 16; ++t) {
-        const int dh = (int)(int8_t)(a.taps[t] & 0xff), dw = (int)(int8_t)((a.taps[t] >> 8) & 0xff);
+        const int dh = tap_dh(a.taps[t]), dw = tap_dw(a.taps[t]);
         if (dh != t / 4 - 1 || dw != t % 4 - 1) return false;
     }
     return d1_strip_rows(a) > 0;
@@ -221,12 +205,7 @@ int launch_conv_d1(const ConvArgs &a0, hipStream_t stream) {
     sa.nstrips = a.Ho / sa.R;
     a.tiles_n = a.Co / 64;
     a.tiles_m = a.N * sa.nstrips;
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(conv_d1_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)D1_LDS);
-        if (e != hipSuccess) DL_FAIL("dl_conv_forward(d1): hipFuncSetAttribute(%zu): %s", D1_LDS, hipGetErrorString(e));
-        attr_set = true;
-    }
+    if (dl_lds_limit(reinterpret_cast<const void *>(conv_d1_kernel), D1_LDS, "dl_conv_forward(d1)")) return -1;
     hipLaunchKernelGGL(conv_d1_kernel, dim3(a.tiles_m * a.tiles_n), dim3(256), D1_LDS, stream, sa);
     DL_CHECK_LAUNCH("dl_conv_forward(d1)");
     return 0;

@@ -11,12 +11,6 @@
 // Same descriptor and packed weights as the four-phase paths (n_phase = 4, per-phase tap lists and weight column bases): no host change beyond the dispatch.
 #include "conv_args.h"
 
-typedef __attribute__((ext_vector_type(16))) float f32x16_t;
-typedef __attribute__((address_space(3))) char lds_char_t;
-typedef __attribute__((address_space(3))) const bf16x8_t lds_frag_t;
-
-template <int V> struct D1GIC { static constexpr int value = V; };
-
 struct D1gArgs {
     ConvArgs a;
     int R, nstrips, segs;
@@ -81,8 +75,8 @@ __global__ void __launch_bounds__(256, 2) conv_d1g_kernel(const D1gArgs sa) {
         const bool real = r >= 0 && r < a.Hi;
         const __amdgpu_buffer_rsrc_t rs = real ? rsrc_in : rsrc_none;
         const int soff = real ? r * (int)row_bytes : 0;
-        stage_piece(D1GIC<0>{}, soff, slot, rs); stage_piece(D1GIC<1>{}, soff, slot, rs); stage_piece(D1GIC<2>{}, soff, slot, rs);
-        stage_piece(D1GIC<3>{}, soff, slot, rs); stage_piece(D1GIC<4>{}, soff, slot, rs);
+        stage_piece(IC<0>{}, soff, slot, rs); stage_piece(IC<1>{}, soff, slot, rs); stage_piece(IC<2>{}, soff, slot, rs);
+        stage_piece(IC<3>{}, soff, slot, rs); stage_piece(IC<4>{}, soff, slot, rs);
     };
 
     // ---- fragment addressing: the wave's pixel w = w0 + wave*32 + lr; offset dw reads LDS pixel q = wave*32 + lr + 1 + dw; ^ (s << 5) for the 16-channel chunk
@@ -144,7 +138,7 @@ static bool d1g_tap_table(const ConvArgs &a, int (&kb)[4][3][3]) {
         if (nt != 4) return false;
         for (int t = 0; t < nt; ++t) {
             const int16_t tp = a.taps[a.phase_tap_begin[p] + t];
-            const int dh = (int)(int8_t)(tp & 0xff), dw = (int)(int8_t)((tp >> 8) & 0xff);
+            const int dh = tap_dh(tp), dw = tap_dw(tp);
             if (dh < -1 || dh > 1 || dw < -1 || dw > 1 || kb[p][dh + 1][dw + 1] >= 0) return false;
             kb[p][dh + 1][dw + 1] = a.phase_kbase[p] + t * a.Ci;
         }
@@ -152,17 +146,8 @@ static bool d1g_tap_table(const ConvArgs &a, int (&kb)[4][3][3]) {
     return true;
 }
 
-static int d1g_strip_rows(const ConvArgs &a) {
-    const int per_img = a.N * (a.Wq / 128);
-    int best = 0;
-    for (int R = 1; R <= a.Hq; ++R) {
-        if (a.Hq % R) continue;
-        const int wgs = per_img * (a.Hq / R);
-        if (best == 0 || wgs >= 480) best = R;
-        if (wgs < 480) break;
-    }
-    return best;
-}
+// strip height: a divisor of Hq that gives the grid about two workgroups per CU
+static int d1g_strip_rows(const ConvArgs &a) { return strip_rows(a.N * (a.Wq / 128), a.Hq, 1, 480); }
 
 // The layer this kernel serves: four sub-pixel phases (out_step 2, in_step 1) of a 4 x 4 stride-2 layer, exact 2x geometry, zero padding, exactly 64 contracted
 // channels, 8 (padded) output channels, phase-grid rows that are multiples of 128 pixels, bf16, no bias / activation / split-K / raw accumulators / statistics.
@@ -172,7 +157,7 @@ bool d1g_eligible(const ConvArgs &a) {
     if (a.Ci != 64 || a.Co != 8 || a.pad_mode != DL_PAD_ZERO || a.bn_y != nullptr || a.in_act != DL_ACT_NONE || a.act != DL_ACT_NONE || a.bias != nullptr ||
         a.stats_part != nullptr)
         return false;
-    if ((size_t)a.Hi * a.Wi * (size_t)a.in_pstride * 2 >= ((size_t)1 << 31) || (size_t)a.Ho * a.Wo * (size_t)a.out_pstride * 2 >= ((size_t)1 << 31)) return false;
+    if (!conv_fits_i32(a)) return false;
     int kb[4][3][3];
     return d1g_tap_table(a, kb) && d1g_strip_rows(a) > 0;
 }
@@ -186,12 +171,7 @@ int launch_conv_d1g(const ConvArgs &a0, hipStream_t stream) {
     sa.R = d1g_strip_rows(a);
     sa.nstrips = a.Hq / sa.R;
     sa.segs = a.Wq / 128;
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(conv_d1g_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)D1G_LDS);
-        if (e != hipSuccess) DL_FAIL("dl_conv_forward(d1g): hipFuncSetAttribute(%zu): %s", D1G_LDS, hipGetErrorString(e));
-        attr_set = true;
-    }
+    if (dl_lds_limit(reinterpret_cast<const void *>(conv_d1g_kernel), D1G_LDS, "dl_conv_forward(d1g)")) return -1;
     hipLaunchKernelGGL(conv_d1g_kernel, dim3(a.N * sa.segs * sa.nstrips), dim3(256), D1G_LDS, stream, sa);
     DL_CHECK_LAUNCH("dl_conv_forward(d1g)");
     return 0;

@@ -110,8 +110,8 @@ static void dot_fill(DotArgs &da, const ConvArgs &a) {
     da.ntaps = a.phase_tap_begin[1] - a.phase_tap_begin[0];
     da.w_kstride = a.w_kstride; da.act = a.act; da.npix = a.N * a.Ho * a.Wo;
     for (int t = 0; t < da.ntaps; ++t) {
-        da.dh[t] = (int8_t)(a.taps[a.phase_tap_begin[0] + t] & 0xff);
-        da.dw[t] = (int8_t)((a.taps[a.phase_tap_begin[0] + t] >> 8) & 0xff);
+        da.dh[t] = tap_dh(a.taps[a.phase_tap_begin[0] + t]);
+        da.dw[t] = tap_dw(a.taps[a.phase_tap_begin[0] + t]);
     }
 }
 

@@ -14,33 +14,6 @@
 
 #include "conv_args.h"
 
-// conv_w4.hip: the one-wave-per-SIMD kernel of the ResnetBlock shape
-bool w4_eligible(const ConvArgs &a);
-int launch_conv_w4(const ConvArgs &a0, hipStream_t stream);
-// conv_w4x3.hip: the same tile for the strict policy (split-copy activations, hi / lo weight images, three MFMAs per product)
-bool w4x3_eligible(const ConvArgs &a);
-int launch_conv_w4x3(const ConvArgs &a0, hipStream_t stream);
-// conv_s2f.hip: the fused four-phase tile of the stride-2 layers (transposed conv forward, stride-2 data gradients)
-bool s2f_eligible(const ConvArgs &a);
-int s2f_stats_chunks(const ConvArgs &a);
-int launch_conv_s2f(const ConvArgs &a0, hipStream_t stream);
-// conv_s2f_x3.hip: the same tile under the strict policy (split-copy input, three products)
-bool d1g_eligible(const ConvArgs &a);
-int launch_conv_d1g(const ConvArgs &a0, hipStream_t stream);
-bool d1_eligible(const ConvArgs &a);
-int launch_conv_d1(const ConvArgs &a0, hipStream_t stream);
-bool dot_fwd_eligible(const ConvArgs &a);
-bool dot_dgrad_eligible(const ConvArgs &a);
-int launch_conv_dot(const ConvArgs &a, bool fwd, hipStream_t stream);
-bool s2u_eligible(const ConvArgs &a);
-int s2u_stats_chunks(const ConvArgs &a);
-int launch_conv_s2u(const ConvArgs &a0, hipStream_t stream);
-bool s2d_eligible(const ConvArgs &a);
-int s2d_stats_chunks(const ConvArgs &a);
-int launch_conv_s2d(const ConvArgs &a0, hipStream_t stream);
-bool s2f_x3_eligible(const ConvArgs &a);
-int launch_conv_s2f_x3(const ConvArgs &a0, hipStream_t stream);
-
 // raw staging registers for one 8-element chunk
 template <typename T> struct Raw8;
 template <> struct Raw8<bf16_t> { u32x4_t v; };
@@ -149,8 +122,8 @@ __global__ void __launch_bounds__(256) conv_gemm_kernel(const ConvArgs a) {
         const bool tap_ok = tl < ntaps;
         if (tap_ok) {
             const int16_t t = tap_lds[tap0 + tl];
-            dh = (int)(int8_t)(t & 0xff);
-            dw = (int)(int8_t)((t >> 8) & 0xff);
+            dh = tap_dh(t);
+            dw = tap_dw(t);
         }
 #pragma unroll
         for (int i = 0; i < X_CH; ++i) {
@@ -658,7 +631,7 @@ __global__ void __launch_bounds__(WM * WN * 64) conv_gemm_glds_kernel(const Conv
     if (tid < DL_MAX_TAPS) {
         const int16_t tp = a.taps[tid];
         tap_lds[tid] = tp;
-        tapd_lds[tid] = ((int)(int8_t)(tp & 0xff) * a.Wi + (int)(int8_t)((tp >> 8) & 0xff)) * a.in_pstride;
+        tapd_lds[tid] = (tap_dh(tp) * a.Wi + tap_dw(tp)) * a.in_pstride;
     }
 
     const bf16_t *in = reinterpret_cast<const bf16_t *>(a.in);
@@ -687,7 +660,7 @@ __global__ void __launch_bounds__(WM * WN * 64) conv_gemm_glds_kernel(const Conv
         if (UTAP && x_ok[i]) {               // (the generic path checks bounds per chunk instead: many taps, short K loops)
             for (int t = 0; t < ntaps; ++t) {
                 const int16_t tp = a.taps[tap0 + t];
-                const int hi = x_hi0[i] + (int)(int8_t)(tp & 0xff), wi = x_wi0[i] + (int)(int8_t)((tp >> 8) & 0xff);
+                const int hi = x_hi0[i] + tap_dh(tp), wi = x_wi0[i] + tap_dw(tp);
                 if (a.pad_mode != DL_PAD_ZERO || (((unsigned)hi < (unsigned)a.Hi) && ((unsigned)wi < (unsigned)a.Wi))) mk |= 1ull << t;
             }
         }
@@ -739,7 +712,7 @@ __global__ void __launch_bounds__(WM * WN * 64) conv_gemm_glds_kernel(const Conv
                     const int ci = k0 & (a.Ci - 1);
                     const int tli = tl < ntaps ? tl : 0;
                     const int16_t t = tap_lds[tap0 + tli];
-                    const int dh = (int)(int8_t)(t & 0xff), dw = (int)(int8_t)((t >> 8) & 0xff);
+                    const int dh = tap_dh(t), dw = tap_dw(t);
                     int hi = x_hi0[i] + dh, wi = x_wi0[i] + dw;
                     if (a.pad_mode != DL_PAD_ZERO) { hi = border_idx(a.pad_mode, hi, a.Hi); wi = border_idx(a.pad_mode, wi, a.Wi); }
                     const bool ok = x_ok[i] && (tl < ntaps) && ((unsigned)hi < (unsigned)a.Hi) && ((unsigned)wi < (unsigned)a.Wi);
@@ -866,7 +839,6 @@ __global__ void __launch_bounds__(WM * WN * 64) conv_gemm_glds_kernel(const Conv
 //   after when those reads were retired (lgkmcnt) before the reading phase's first barrier (WB_0: the lgkmcnt(8) in phase 0).
 // ------------------------------------------------------------------------------------------------------------------
 #define DL_BAR() asm volatile("s_barrier" ::: "memory")
-template <int V> struct IC { static constexpr int value = V; };
 
 template <int ABL>      // ABL != 0: timing-only ablations (tools/ablate.sh): 1 = no DMA in the loop, 2 = no ds_reads / MFMAs, 3 = MFMAs only
 __global__ void __launch_bounds__(512) conv_gemm_8ph_kernel(const ConvArgs a) {
@@ -897,7 +869,7 @@ __global__ void __launch_bounds__(512) conv_gemm_8ph_kernel(const ConvArgs a) {
 
     if (tid < DL_MAX_TAPS) {
         const int16_t tp = a.taps[tid];
-        tapd_lds[tid] = ((int)(int8_t)(tp & 0xff) * a.Wi + (int)(int8_t)((tp >> 8) & 0xff)) * a.in_pstride;
+        tapd_lds[tid] = (tap_dh(tp) * a.Wi + tap_dw(tp)) * a.in_pstride;
     }
 
     const bf16_t *in = reinterpret_cast<const bf16_t *>(a.in);
@@ -927,7 +899,7 @@ __global__ void __launch_bounds__(512) conv_gemm_8ph_kernel(const ConvArgs a) {
                 if (ok)
                     for (int t = 0; t < ntaps; ++t) {
                         const int16_t tp = a.taps[tap0 + t];
-                        const int hi = hi0 + (int)(int8_t)(tp & 0xff), wi = wi0 + (int)(int8_t)((tp >> 8) & 0xff);
+                        const int hi = hi0 + tap_dh(tp), wi = wi0 + tap_dw(tp);
                         if (((unsigned)hi < (unsigned)a.Hi) && ((unsigned)wi < (unsigned)a.Wi)) mk |= 1ull << t;
                     }
                 x_mask[h][i] = mk;
@@ -1113,12 +1085,7 @@ static int launch_conv_8ph(const ConvArgs &a0, hipStream_t stream) {
     a.k_order8 = (korder && korder[0] == '0') ? 0 : 1;
     constexpr size_t smem_loop = (size_t)8 * 128 * 64 * sizeof(bf16_t) + DL_MAX_TAPS * sizeof(int);
     constexpr size_t smem = smem_loop > epilogue_lds_bytes<256, 256, 2>() ? smem_loop : epilogue_lds_bytes<256, 256, 2>();
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(conv_gemm_8ph_kernel<ABL>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-        if (e != hipSuccess) DL_FAIL("dl_conv_forward: hipFuncSetAttribute(%zu): %s", smem, hipGetErrorString(e));
-        attr_set = true;
-    }
+    if (dl_lds_limit(reinterpret_cast<const void *>(conv_gemm_8ph_kernel<ABL>), smem, "dl_conv_forward")) return -1;
     dim3 grid(a.tiles_m * a.tiles_n, a.n_phase * a.splitk);
     hipLaunchKernelGGL(conv_gemm_8ph_kernel<ABL>, grid, dim3(512), smem, stream, a);
     DL_CHECK_LAUNCH("dl_conv_forward(8-phase)");
@@ -1138,8 +1105,6 @@ static int launch_conv_8ph(const ConvArgs &a0, hipStream_t stream) {
 //   down: 32 KB of activation DMA per THREE K tiles instead of per tile (-33% of all staged bytes; the DMA path, ~18 B/clk/CU
 //   whatever the depth, is what bounds these kernels).  K tiles run in (kh, chunk, kw) order.
 // ------------------------------------------------------------------------------------------------------------------
-typedef __attribute__((ext_vector_type(16))) float f32x16_t;
-
 template <bool KWR, int ABL>
 __global__ void __launch_bounds__(512) conv_gemm_p32_kernel(const ConvArgs a) {
     constexpr int BM = 256, BN = 256, BK = 64, CPR = 8;
@@ -1170,7 +1135,7 @@ __global__ void __launch_bounds__(512) conv_gemm_p32_kernel(const ConvArgs a) {
 
     if (tid < DL_MAX_TAPS) {
         const int16_t tp = a.taps[tid];
-        const int dh = (int)(int8_t)(tp & 0xff), dw = (int)(int8_t)((tp >> 8) & 0xff);
+        const int dh = tap_dh(tp), dw = tap_dw(tp);
         tapd_lds[tid] = (dh * a.Wi + (KWR ? 0 : dw)) * a.in_pstride;
         tapw_lds[tid] = dw + 1;
     }
@@ -1215,7 +1180,7 @@ __global__ void __launch_bounds__(512) conv_gemm_p32_kernel(const ConvArgs a) {
         if (ok)
             for (int t = 0; t < ntaps; ++t) {
                 const int16_t tp = a.taps[tap0 + t];
-                const int hi = hi0 + (int)(int8_t)(tp & 0xff), wi = wi0 + (KWR ? 0 : (int)(int8_t)((tp >> 8) & 0xff));
+                const int hi = hi0 + tap_dh(tp), wi = wi0 + (KWR ? 0 : tap_dw(tp));
                 if (((unsigned)hi < (unsigned)a.Hi) && ((unsigned)wi < (unsigned)a.Wi)) mk |= 1ull << t;
             }
         x_mask[i] = mk;
@@ -1465,12 +1430,7 @@ static int launch_conv_p32(const ConvArgs &a0, hipStream_t stream) {
     a.tiles_n = a.Co / 256;
     constexpr size_t smem = (size_t)2 * (KWR ? 260 : 256) * 128 + (size_t)2 * 256 * 128 + 2 * DL_MAX_TAPS * sizeof(int);
     auto kern = conv_gemm_p32_kernel<KWR, ABL>;
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-        if (e != hipSuccess) DL_FAIL("dl_conv_forward: hipFuncSetAttribute(%zu): %s", smem, hipGetErrorString(e));
-        attr_set = true;
-    }
+    if (dl_lds_limit(reinterpret_cast<const void *>(kern), smem, "dl_conv_forward")) return -1;
     dim3 grid(a.tiles_m * a.tiles_n, a.n_phase * a.splitk);
     hipLaunchKernelGGL(kern, grid, dim3(512), smem, stream, a);
     DL_CHECK_LAUNCH("dl_conv_forward(p32)");
@@ -1483,11 +1443,11 @@ static bool kwr_eligible(const ConvArgs &a) {
     if (a.n_phase != 1 || a.splitk != 1 || a.in_step != 1 || a.out_step != 1 || a.Wq != 128 || a.Wi != 128 || (a.Hq & 1)) return false;
     if (a.phase_tap_begin[1] - a.phase_tap_begin[0] != 9 || a.Ci < 64) return false;
     for (int kh = 0; kh < 3; ++kh) {
-        const int dh0 = (int8_t)(a.taps[kh * 3] & 0xff);
+        const int dh0 = tap_dh(a.taps[kh * 3]);
         int seen = 0;
         for (int kw = 0; kw < 3; ++kw) {
             const int16_t tp = a.taps[kh * 3 + kw];
-            const int dh = (int8_t)(tp & 0xff), dw = (int8_t)((tp >> 8) & 0xff);
+            const int dh = tap_dh(tp), dw = tap_dw(tp);
             if (dh != dh0 || dw < -1 || dw > 1) return false;
             seen |= 1 << (dw + 1);
         }
@@ -1511,12 +1471,7 @@ static int launch_conv_glds_impl(const ConvArgs &a0, hipStream_t stream) {
     constexpr size_t smem_loop = (size_t)2 * (BM + BN) * BK * sizeof(bf16_t) + DL_MAX_TAPS * (sizeof(int16_t) + sizeof(int));
     constexpr size_t smem = (BN >= 64 && epilogue_lds_bytes<BM, BN, WM>() > smem_loop) ? epilogue_lds_bytes<BM, BN, WM>() : smem_loop;
     auto kern = conv_gemm_glds_kernel<BM, BN, BK, WM, WN, UTAP, STAG, ABL>;
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-        if (e != hipSuccess) DL_FAIL("dl_conv_forward: hipFuncSetAttribute(%zu): %s", smem, hipGetErrorString(e));
-        attr_set = true;
-    }
+    if (dl_lds_limit(reinterpret_cast<const void *>(kern), smem, "dl_conv_forward")) return -1;
     dim3 grid(a.tiles_m * a.tiles_n, a.n_phase * a.splitk);
     hipLaunchKernelGGL(kern, grid, dim3(WM * WN * 64), smem, stream, a);
     DL_CHECK_LAUNCH("dl_conv_forward(glds)");
@@ -1620,12 +1575,7 @@ static int launch_conv(const ConvArgs &a0, hipStream_t stream) {
     constexpr int NPL = (PREC == 3) ? 2 : 1;
     constexpr size_t smem = (size_t)2 * NPL * (BM + BN) * BK * sizeof(bf16_t) + DL_MAX_TAPS * sizeof(int16_t);
     auto kern = conv_gemm_kernel<TIn, TOut, PREC, BM, BN, BK, WM, WN>;
-    static bool attr_set = false;      // benign race: idempotent
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-        if (e != hipSuccess) DL_FAIL("dl_conv_forward: hipFuncSetAttribute(%zu): %s", smem, hipGetErrorString(e));
-        attr_set = true;
-    }
+    if (dl_lds_limit(reinterpret_cast<const void *>(kern), smem, "dl_conv_forward")) return -1;
     dim3 grid(a.tiles_m * a.tiles_n, a.n_phase * a.splitk);
     hipLaunchKernelGGL(kern, grid, dim3(256), smem, stream, a);
     DL_CHECK_LAUNCH("dl_conv_forward");

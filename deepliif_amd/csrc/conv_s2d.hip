@@ -21,13 +21,7 @@
 // Same descriptor and packed weights as the gather GEMM (n_phase = 1, in_step = 2, taps (kh - 1, kw - 1) kh-major): no host change beyond the dispatch.
 #include "conv_args.h"
 
-typedef __attribute__((ext_vector_type(16))) float f32x16_t;
-typedef __attribute__((address_space(3))) char lds_char_t;
-typedef __attribute__((address_space(3))) const bf16x8_t lds_frag_t;
-
 __device__ __attribute__((aligned(64))) unsigned char g_s2d_zero_page[64];
-
-template <int V> struct S2DIC { static constexpr int value = V; };
 
 struct S2dArgs {
     ConvArgs a;
@@ -120,9 +114,9 @@ __global__ void __launch_bounds__(256) conv_s2d_kernel(const S2dArgs sa) {
     };
     auto stage = [&](int r, int slot) __attribute__((always_inline)) {       // input row r of the image -> ring slot, all pieces at once (prologue)
         const int rowp = r * (int)row_bytes;
-        stage_piece(S2DIC<0>{}, rowp, slot, rsrc_in); stage_piece(S2DIC<1>{}, rowp, slot, rsrc_in); stage_piece(S2DIC<2>{}, rowp, slot, rsrc_in);
-        stage_piece(S2DIC<3>{}, rowp, slot, rsrc_in); stage_piece(S2DIC<4>{}, rowp, slot, rsrc_in); stage_piece(S2DIC<5>{}, rowp, slot, rsrc_in);
-        stage_piece(S2DIC<6>{}, rowp, slot, rsrc_in); stage_piece(S2DIC<7>{}, rowp, slot, rsrc_in); stage_piece(S2DIC<8>{}, rowp, slot, rsrc_in);
+        stage_piece(IC<0>{}, rowp, slot, rsrc_in); stage_piece(IC<1>{}, rowp, slot, rsrc_in); stage_piece(IC<2>{}, rowp, slot, rsrc_in);
+        stage_piece(IC<3>{}, rowp, slot, rsrc_in); stage_piece(IC<4>{}, rowp, slot, rsrc_in); stage_piece(IC<5>{}, rowp, slot, rsrc_in);
+        stage_piece(IC<6>{}, rowp, slot, rsrc_in); stage_piece(IC<7>{}, rowp, slot, rsrc_in); stage_piece(IC<8>{}, rowp, slot, rsrc_in);
     };
 
     // ---- fragment addressing (bytes inside a slot): lane = (pixel lr of a 32-pixel block, K half lh); + j * 4096 (pixel block), ^ (s << 5) (K sub-step)
@@ -149,16 +143,16 @@ __global__ void __launch_bounds__(256) conv_s2d_kernel(const S2dArgs sa) {
             constexpr int g = decltype(Gc)::value, kw = g >> 2, sx = g & 3;
             if constexpr (g + 1 < 12) read_group(Fn, base + (frag_base((g + 1) >> 2) ^ (((g + 1) & 3) << 5)));
             else if (slot_next >= 0) read_group(Fn, slot_next * S2D_SLOT + a_kw0);
-            if constexpr (g < 9) stage_piece(S2DIC<(g < 9 ? g : 0)>{}, soff_dma, slot_dma, rsrc_dma);
+            if constexpr (g < 9) stage_piece(IC<(g < 9 ? g : 0)>{}, soff_dma, slot_dma, rsrc_dma);
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 if constexpr (khc >= 0) cur[j] = dl_mfma32(W[khc < 0 ? 0 : khc][kw][sx], Fc[j], cur[j]);
                 if constexpr (khn >= 0) nxt[j] = dl_mfma32(W[khn < 0 ? 0 : khn][kw][sx], Fc[j], nxt[j]);
             }
         };
-        group(S2DIC<0>{}, F0, F1); group(S2DIC<1>{}, F1, F0); group(S2DIC<2>{}, F0, F1); group(S2DIC<3>{}, F1, F0);
-        group(S2DIC<4>{}, F0, F1); group(S2DIC<5>{}, F1, F0); group(S2DIC<6>{}, F0, F1); group(S2DIC<7>{}, F1, F0);
-        group(S2DIC<8>{}, F0, F1); group(S2DIC<9>{}, F1, F0); group(S2DIC<10>{}, F0, F1); group(S2DIC<11>{}, F1, F0);
+        group(IC<0>{}, F0, F1); group(IC<1>{}, F1, F0); group(IC<2>{}, F0, F1); group(IC<3>{}, F1, F0);
+        group(IC<4>{}, F0, F1); group(IC<5>{}, F1, F0); group(IC<6>{}, F0, F1); group(IC<7>{}, F1, F0);
+        group(IC<8>{}, F0, F1); group(IC<9>{}, F1, F0); group(IC<10>{}, F0, F1); group(IC<11>{}, F1, F0);
     };
 
     // ---- epilogue state.  The accumulators START at the bias (re-read from L1 / L2 after every epilogue: 16 registers that need not live through the
@@ -246,7 +240,7 @@ __global__ void __launch_bounds__(256) conv_s2d_kernel(const S2dArgs sa) {
     asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
     if (r_first >= 0) {
         read_group(FA, 3 * S2D_SLOT + a_kw0);
-        row_mac(S2DIC<0>{}, S2DIC<-1>{}, 3, -1, accA, accB, FA, FB, 0, 2, rsrc_none);      // (the out-of-range pieces write zeros: into slot 2, which is still free)
+        row_mac(IC<0>{}, IC<-1>{}, 3, -1, accA, accB, FA, FB, 0, 2, rsrc_none);      // (the out-of-range pieces write zeros: into slot 2, which is still free)
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");       // slot 3 is about to be refilled
     }
     auto out_row = [&](int t, int s0, f32x16_t (&cur)[4], f32x16_t (&nxt)[4]) __attribute__((always_inline)) {
@@ -255,9 +249,9 @@ __global__ void __launch_bounds__(256) conv_s2d_kernel(const S2dArgs sa) {
         const int soff = (2 * ho + 2) * (int)row_bytes;
         read_group(FA, s0 * S2D_SLOT + a_kw0);
         const __amdgpu_buffer_rsrc_t rs = more ? rsrc_in : rsrc_none;
-        row_mac(S2DIC<1>{}, S2DIC<-1>{}, s0, s0 + 1, cur, nxt, FA, FB, soff, s0 ^ 2, rs);
+        row_mac(IC<1>{}, IC<-1>{}, s0, s0 + 1, cur, nxt, FA, FB, soff, s0 ^ 2, rs);
         // (the strip's last row also feeds `nxt`, which nobody uses: 48 of 2 352 MFMAs per wave instead of a second code path that costs accumulator copies)
-        row_mac(S2DIC<2>{}, S2DIC<0>{}, s0 + 1, -1, cur, nxt, FA, FB, soff + (int)row_bytes, (s0 ^ 2) + 1, rs);
+        row_mac(IC<2>{}, IC<0>{}, s0 + 1, -1, cur, nxt, FA, FB, soff + (int)row_bytes, (s0 ^ 2) + 1, rs);
         __builtin_amdgcn_sched_barrier(0);       // the row's MFMAs stay in front of the epilogue that reads their accumulators
         epilogue(cur, ho);
         __builtin_amdgcn_sched_barrier(0);
@@ -294,18 +288,7 @@ __global__ void __launch_bounds__(256) conv_s2d_kernel(const S2dArgs sa) {
 }
 
 // strip height: an even divisor of Ho that gives the grid about one workgroup per CU (each strip re-reads one halo row, so taller is cheaper)
-static int s2d_strip_rows(const ConvArgs &a) {
-    const int segs = a.Wo / 128, tiles_n = a.Co / 128;
-    const int per_img = a.N * segs * tiles_n;
-    int best = 0;
-    for (int R = 2; R <= a.Ho; R += 2) {
-        if (a.Ho % R) continue;
-        const int wgs = per_img * (a.Ho / R);
-        if (best == 0 || wgs >= 240) best = R;          // the tallest strip that still fills the chip; else the smallest even divisor
-        if (wgs < 240) break;
-    }
-    return best;
-}
+static int s2d_strip_rows(const ConvArgs &a) { return strip_rows(a.N * (a.Wo / 128) * (a.Co / 128), a.Ho, 2, 240); }
 
 // The layers this kernel serves: one phase, input step 2, the nine taps (kh - 1, kw - 1) kh-major, zero padding, exactly 64 contracted channels, output
 // channels a multiple of 128, exact 2x geometry with output rows that are multiples of 128 pixels, bf16, no split-K / raw accumulators / input activation.
@@ -315,9 +298,9 @@ bool s2d_eligible(const ConvArgs &a) {
     if (a.Hi != 2 * a.Ho || a.Wi != 2 * a.Wo || a.Hq != a.Ho || a.Wq != a.Wo || (a.Wo & 127) || (a.Ho & 1)) return false;
     if (a.pad_mode != DL_PAD_ZERO || a.bn_y != nullptr || a.in_act != DL_ACT_NONE || a.epi_old) return false;
     if (a.act != DL_ACT_NONE && a.act != DL_ACT_RELU) return false;
-    if ((size_t)a.Hi * a.Wi * (size_t)a.in_pstride * 2 >= ((size_t)1 << 31) || (size_t)a.Ho * a.Wo * (size_t)a.out_pstride * 2 >= ((size_t)1 << 31)) return false;      // 32-bit offsets
+    if (!conv_fits_i32(a)) return false;
     for (int t = 0; t < 9; ++t) {
-        const int dh = (int)(int8_t)(a.taps[t] & 0xff), dw = (int)(int8_t)((a.taps[t] >> 8) & 0xff);
+        const int dh = tap_dh(a.taps[t]), dw = tap_dw(a.taps[t]);
         if (dh != t / 3 - 1 || dw != t % 3 - 1) return false;
     }
     return s2d_strip_rows(a) > 0;
@@ -341,24 +324,12 @@ int launch_conv_s2d(const ConvArgs &a0, hipStream_t stream) {
     a.tiles_n = a.Co / 128;
     a.tiles_m = a.N * sa.segs * sa.nstrips;
     if (a.stats_part && a.stats_nchunks != sa.segs * sa.nstrips) DL_FAIL("dl_conv_forward(s2d): statistics chunks %d != %d", a.stats_nchunks, sa.segs * sa.nstrips);
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipSuccess;
-        const void *fns[4] = {reinterpret_cast<const void *>(conv_s2d_kernel<false, false>), reinterpret_cast<const void *>(conv_s2d_kernel<false, true>),
-                              reinterpret_cast<const void *>(conv_s2d_kernel<true, false>), reinterpret_cast<const void *>(conv_s2d_kernel<true, true>)};
-        for (int i = 0; i < 4 && e == hipSuccess; ++i) e = hipFuncSetAttribute(fns[i], hipFuncAttributeMaxDynamicSharedMemorySize, (int)S2D_LDS);
-        if (e != hipSuccess) DL_FAIL("dl_conv_forward(s2d): hipFuncSetAttribute(%zu): %s", S2D_LDS, hipGetErrorString(e));
-        attr_set = true;
-    }
-    dim3 grid(a.tiles_m * a.tiles_n, 1);
     const bool relu = a.act == DL_ACT_RELU;
-    if (a.stats_part) {
-        if (relu) hipLaunchKernelGGL((conv_s2d_kernel<true, true>), grid, dim3(256), S2D_LDS, stream, sa);
-        else hipLaunchKernelGGL((conv_s2d_kernel<true, false>), grid, dim3(256), S2D_LDS, stream, sa);
-    } else {
-        if (relu) hipLaunchKernelGGL((conv_s2d_kernel<false, true>), grid, dim3(256), S2D_LDS, stream, sa);
-        else hipLaunchKernelGGL((conv_s2d_kernel<false, false>), grid, dim3(256), S2D_LDS, stream, sa);
-    }
+    // (<false, false> named first: the order of first use is the order of the four kernels in the code object)
+    void (*kern)(const S2dArgs) = !a.stats_part ? (!relu ? conv_s2d_kernel<false, false> : conv_s2d_kernel<false, true>)
+                                                : (!relu ? conv_s2d_kernel<true, false> : conv_s2d_kernel<true, true>);
+    if (dl_lds_limit(reinterpret_cast<const void *>(kern), S2D_LDS, "dl_conv_forward(s2d)")) return -1;
+    hipLaunchKernelGGL(kern, dim3(a.tiles_m * a.tiles_n, 1), dim3(256), S2D_LDS, stream, sa);
     DL_CHECK_LAUNCH("dl_conv_forward(s2d)");
     return 0;
 }

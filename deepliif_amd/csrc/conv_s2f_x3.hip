@@ -13,13 +13,7 @@
 // Inputs that are not split copies stay on the 4-phase kernel.
 #include "conv_args.h"
 
-typedef __attribute__((ext_vector_type(16))) float f32x16_t;
-typedef __attribute__((address_space(3))) char lds_char_t;
-typedef __attribute__((address_space(3))) const bf16x8_t lds_frag_t;
-
 __device__ __attribute__((aligned(64))) unsigned char g_s2fx3_zero_page[64];
-
-template <int V> struct S3IC { static constexpr int value = V; };
 
 constexpr int S3_MAX_OFF = 9;
 struct S2fX3Args {
@@ -252,8 +246,8 @@ __global__ void __launch_bounds__(512) conv_s2f_x3_kernel(const S2fX3Args sa) {
         }
         __syncthreads();
     };
-    pass(S3IC<0>{});
-    pass(S3IC<1>{});
+    pass(IC<0>{});
+    pass(IC<1>{});
 
     if (want_stats && tid < 64) {
         // every pixel of this tile lies in ONE image (s2f_stats_chunks): one chunk per tile
@@ -324,20 +318,15 @@ int launch_conv_s2f_x3(const ConvArgs &a0, hipStream_t stream) {
             if (o < 0) {
                 o = no++;
                 key[o] = a.taps[t];
-                sa.off_dh[o] = (int8_t)(a.taps[t] & 0xff);
-                sa.off_dw[o] = (int8_t)((a.taps[t] >> 8) & 0xff);
+                sa.off_dh[o] = tap_dh(a.taps[t]);
+                sa.off_dw[o] = tap_dw(a.taps[t]);
                 sa.off_delta[o] = ((int)sa.off_dh[o] * a.Wi + (int)sa.off_dw[o]) * a.in_pstride;
                 for (int q = 0; q < 4; ++q) sa.user_k[o][q] = -1;
             }
             sa.user_k[o][p] = a.phase_kbase[p] + (t - a.phase_tap_begin[p]) * a.Ci;
         }
     sa.n_off = no;
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(conv_s2f_x3_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)S3_LDS);
-        if (e != hipSuccess) DL_FAIL("dl_conv_forward(s2f_x3): hipFuncSetAttribute(%zu): %s", S3_LDS, hipGetErrorString(e));
-        attr_set = true;
-    }
+    if (dl_lds_limit(reinterpret_cast<const void *>(conv_s2f_x3_kernel), S3_LDS, "dl_conv_forward(s2f_x3)")) return -1;
     dim3 grid(a.tiles_m * a.tiles_n, 1);
     hipLaunchKernelGGL(conv_s2f_x3_kernel, grid, dim3(512), S3_LDS, stream, sa);
     DL_CHECK_LAUNCH("dl_conv_forward(s2f_x3)");

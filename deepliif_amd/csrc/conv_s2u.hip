@@ -17,12 +17,6 @@
 // Same descriptor and packed weights as the four-phase paths (n_phase = 4, per-phase tap lists and weight column bases): no host change beyond the dispatch.
 #include "conv_args.h"
 
-typedef __attribute__((ext_vector_type(16))) float f32x16_t;
-typedef __attribute__((address_space(3))) char lds_char_t;
-typedef __attribute__((address_space(3))) const bf16x8_t lds_frag_t;
-
-template <int V> struct S2UIC { static constexpr int value = V; };
-
 struct S2uArgs {
     ConvArgs a;
     int R, nstrips, segs;
@@ -93,8 +87,8 @@ __global__ void __launch_bounds__(256) conv_s2u_kernel(const S2uArgs sa) {
     auto stage = [&](int r, int slot) __attribute__((always_inline)) {          // input row r (a row below the image: zeros) -> ring slot
         const __amdgpu_buffer_rsrc_t rs = r < a.Hi ? rsrc_in : rsrc_none;
         const int soff = r < a.Hi ? r * (int)row_bytes : 0;
-        stage_piece(S2UIC<0>{}, soff, slot, rs); stage_piece(S2UIC<1>{}, soff, slot, rs); stage_piece(S2UIC<2>{}, soff, slot, rs);
-        stage_piece(S2UIC<3>{}, soff, slot, rs); stage_piece(S2UIC<4>{}, soff, slot, rs);
+        stage_piece(IC<0>{}, soff, slot, rs); stage_piece(IC<1>{}, soff, slot, rs); stage_piece(IC<2>{}, soff, slot, rs);
+        stage_piece(IC<3>{}, soff, slot, rs); stage_piece(IC<4>{}, soff, slot, rs);
     };
 
     // ---- fragment addressing (bytes inside a slot): lane = (pixel lr of a 32-pixel block, K half lh); tap dw reads pixel lr + dw; + j * 8192, ^ (s << 5)
@@ -200,20 +194,20 @@ __global__ void __launch_bounds__(256) conv_s2u_kernel(const S2uArgs sa) {
             auto sub = [&](auto Sc, bf16x8_t (&Fc)[8], bf16x8_t (&Fn)[8]) __attribute__((always_inline)) {
                 constexpr int s = decltype(Sc)::value;
                 if constexpr (s + 1 < 8) read_frags0(Fn, sA, sB, s + 1);
-                if constexpr (s < 5) stage_piece(S2UIC<(s < 5 ? s : 0)>{}, soff_dma, slot_dma, rs);
+                if constexpr (s < 5) stage_piece(IC<(s < 5 ? s : 0)>{}, soff_dma, slot_dma, rs);
 #pragma unroll
                 for (int u = 0; u < 4; ++u)
 #pragma unroll
                     for (int j = 0; j < 2; ++j) acc[0][j] = dl_mfma32(W[u][s], Fc[u * 2 + j], acc[0][j]);
             };
-            sub(S2UIC<0>{}, FA, FB); sub(S2UIC<1>{}, FB, FA); sub(S2UIC<2>{}, FA, FB); sub(S2UIC<3>{}, FB, FA);
-            sub(S2UIC<4>{}, FA, FB); sub(S2UIC<5>{}, FB, FA); sub(S2UIC<6>{}, FA, FB); sub(S2UIC<7>{}, FB, FA);
+            sub(IC<0>{}, FA, FB); sub(IC<1>{}, FB, FA); sub(IC<2>{}, FA, FB); sub(IC<3>{}, FB, FA);
+            sub(IC<4>{}, FA, FB); sub(IC<5>{}, FB, FA); sub(IC<6>{}, FA, FB); sub(IC<7>{}, FB, FA);
         } else {
             read_frags1(FA, sA, sB, 0);
             auto sub = [&](auto Sc, bf16x8_t (&Fc)[8], bf16x8_t (&Fn)[8]) __attribute__((always_inline)) {
                 constexpr int s = decltype(Sc)::value;
                 if constexpr (s + 1 < 8) read_frags1(Fn, sA, sB, s + 1);
-                if constexpr (s < 5) stage_piece(S2UIC<(s < 5 ? s : 0)>{}, soff_dma, slot_dma, rs);
+                if constexpr (s < 5) stage_piece(IC<(s < 5 ? s : 0)>{}, soff_dma, slot_dma, rs);
 #pragma unroll
                 for (int j = 0; j < 2; ++j) {
                     acc[0][j] = dl_mfma32(W[0][s], Fc[0 + j], acc[0][j]);
@@ -223,8 +217,8 @@ __global__ void __launch_bounds__(256) conv_s2u_kernel(const S2uArgs sa) {
                     acc[2][j] = dl_mfma32(W[4][s], Fc[4 + j], acc[2][j]);
                 }
             };
-            sub(S2UIC<0>{}, FA, FB); sub(S2UIC<1>{}, FB, FA); sub(S2UIC<2>{}, FA, FB); sub(S2UIC<3>{}, FB, FA);
-            sub(S2UIC<4>{}, FA, FB); sub(S2UIC<5>{}, FB, FA); sub(S2UIC<6>{}, FA, FB); sub(S2UIC<7>{}, FB, FA);
+            sub(IC<0>{}, FA, FB); sub(IC<1>{}, FB, FA); sub(IC<2>{}, FA, FB); sub(IC<3>{}, FB, FA);
+            sub(IC<4>{}, FA, FB); sub(IC<5>{}, FB, FA); sub(IC<6>{}, FA, FB); sub(IC<7>{}, FB, FA);
         }
     };
 
@@ -272,17 +266,7 @@ __global__ void __launch_bounds__(256) conv_s2u_kernel(const S2uArgs sa) {
 }
 
 // strip height: a divisor of Hq that gives the grid about one workgroup per CU (each strip re-reads one halo row, so taller is cheaper)
-static int s2u_strip_rows(const ConvArgs &a) {
-    const int per_img = a.N * (a.Wq / 64) * (a.Co / 64);
-    int best = 0;
-    for (int R = 1; R <= a.Hq; ++R) {
-        if (a.Hq % R) continue;
-        const int wgs = per_img * (a.Hq / R);
-        if (best == 0 || wgs >= 240) best = R;
-        if (wgs < 240) break;
-    }
-    return best;
-}
+static int s2u_strip_rows(const ConvArgs &a) { return strip_rows(a.N * (a.Wq / 64) * (a.Co / 64), a.Hq, 1, 240); }
 
 // fills kb[p][dh][dw]; false when the descriptor is not the 2 x 2-phase form of a 3 x 3 stride-2 layer (phase (ph, pw) has the taps dh in {0 .. ph}, dw in {0 .. pw})
 static bool s2u_tap_table(const ConvArgs &a, int (&kb)[4][2][2]) {
@@ -294,7 +278,7 @@ static bool s2u_tap_table(const ConvArgs &a, int (&kb)[4][2][2]) {
         if (nt != ((p >> 1) + 1) * ((p & 1) + 1)) return false;
         for (int t = 0; t < nt; ++t) {
             const int16_t tp = a.taps[a.phase_tap_begin[p] + t];
-            const int dh = (int)(int8_t)(tp & 0xff), dw = (int)(int8_t)((tp >> 8) & 0xff);
+            const int dh = tap_dh(tp), dw = tap_dw(tp);
             if (dh < 0 || dh > (p >> 1) || dw < 0 || dw > (p & 1) || kb[p][dh][dw] >= 0) return false;
             kb[p][dh][dw] = a.phase_kbase[p] + t * a.Ci;
         }
@@ -310,7 +294,7 @@ bool s2u_eligible(const ConvArgs &a) {
     if (a.Ho != 2 * a.Hq || a.Wo != 2 * a.Wq || a.Hi != a.Hq || a.Wi != a.Wq || (a.Wq & 63)) return false;
     if (a.Ci != 128 || a.Co < 64 || (a.Co & 63) || a.pad_mode != DL_PAD_ZERO || a.bn_y != nullptr || a.in_act != DL_ACT_NONE || a.epi_old) return false;
     if (a.act != DL_ACT_NONE && a.act != DL_ACT_RELU) return false;
-    if ((size_t)a.Hi * a.Wi * (size_t)a.in_pstride * 2 >= ((size_t)1 << 31) || (size_t)a.Ho * a.Wo * (size_t)a.out_pstride * 2 >= ((size_t)1 << 31)) return false;      // 32-bit offsets
+    if (!conv_fits_i32(a)) return false;
     int kb[4][2][2];
     return s2u_tap_table(a, kb) && s2u_strip_rows(a) > 0;
 }
@@ -334,24 +318,12 @@ int launch_conv_s2u(const ConvArgs &a0, hipStream_t stream) {
     a.tiles_n = a.Co / 64;
     a.tiles_m = a.N * sa.segs * sa.nstrips;
     if (a.stats_part && a.stats_nchunks != sa.segs * sa.nstrips) DL_FAIL("dl_conv_forward(s2u): statistics chunks %d != %d", a.stats_nchunks, sa.segs * sa.nstrips);
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipSuccess;
-        const void *fns[4] = {reinterpret_cast<const void *>(conv_s2u_kernel<false, false>), reinterpret_cast<const void *>(conv_s2u_kernel<false, true>),
-                              reinterpret_cast<const void *>(conv_s2u_kernel<true, false>), reinterpret_cast<const void *>(conv_s2u_kernel<true, true>)};
-        for (int i = 0; i < 4 && e == hipSuccess; ++i) e = hipFuncSetAttribute(fns[i], hipFuncAttributeMaxDynamicSharedMemorySize, (int)S2U_LDS);
-        if (e != hipSuccess) DL_FAIL("dl_conv_forward(s2u): hipFuncSetAttribute(%zu): %s", S2U_LDS, hipGetErrorString(e));
-        attr_set = true;
-    }
-    dim3 grid(a.tiles_m * a.tiles_n, 1);
     const bool relu = a.act == DL_ACT_RELU;
-    if (a.stats_part) {
-        if (relu) hipLaunchKernelGGL((conv_s2u_kernel<true, true>), grid, dim3(256), S2U_LDS, stream, sa);
-        else hipLaunchKernelGGL((conv_s2u_kernel<true, false>), grid, dim3(256), S2U_LDS, stream, sa);
-    } else {
-        if (relu) hipLaunchKernelGGL((conv_s2u_kernel<false, true>), grid, dim3(256), S2U_LDS, stream, sa);
-        else hipLaunchKernelGGL((conv_s2u_kernel<false, false>), grid, dim3(256), S2U_LDS, stream, sa);
-    }
+    // (<false, false> named first: the order of first use is the order of the four kernels in the code object)
+    void (*kern)(const S2uArgs) = !a.stats_part ? (!relu ? conv_s2u_kernel<false, false> : conv_s2u_kernel<false, true>)
+                                                : (!relu ? conv_s2u_kernel<true, false> : conv_s2u_kernel<true, true>);
+    if (dl_lds_limit(reinterpret_cast<const void *>(kern), S2U_LDS, "dl_conv_forward(s2u)")) return -1;
+    hipLaunchKernelGGL(kern, dim3(a.tiles_m * a.tiles_n, 1), dim3(256), S2U_LDS, stream, sa);
     DL_CHECK_LAUNCH("dl_conv_forward(s2u)");
     return 0;
 }

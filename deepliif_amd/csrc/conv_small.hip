@@ -23,7 +23,6 @@
 __device__ __attribute__((aligned(64))) unsigned char g_zero_page_small[64];
 
 #define DLS_BAR() asm volatile("s_barrier" ::: "memory")
-template <int V> struct ICS { static constexpr int value = V; };
 
 // ----------------------------------------------------------------------------------------------------------------------------
 // head forward: rolling rows
@@ -199,13 +198,13 @@ __global__ void __launch_bounds__(640) conv_narrow_roll_kernel(const NarrowArgs 
         for (int s = 0; s < KH; ++s) {
             if (q + 2 * s >= nrows + 2) break;
             switch (s) {       // static S for the accumulator rotation: row q + 2s has S = 2s mod KH
-                case 0: pair_step(q + 0, ICS<0>{}); break;
-                case 1: pair_step(q + 2, ICS<2 % KH>{}); break;
-                case 2: pair_step(q + 4, ICS<4 % KH>{}); break;
-                case 3: pair_step(q + 6, ICS<6 % KH>{}); break;
-                case 4: pair_step(q + 8, ICS<8 % KH>{}); break;
-                case 5: pair_step(q + 10, ICS<10 % KH>{}); break;
-                default: pair_step(q + 12, ICS<12 % KH>{}); break;
+                case 0: pair_step(q + 0, IC<0>{}); break;
+                case 1: pair_step(q + 2, IC<2 % KH>{}); break;
+                case 2: pair_step(q + 4, IC<4 % KH>{}); break;
+                case 3: pair_step(q + 6, IC<6 % KH>{}); break;
+                case 4: pair_step(q + 8, IC<8 % KH>{}); break;
+                case 5: pair_step(q + 10, IC<10 % KH>{}); break;
+                default: pair_step(q + 12, IC<12 % KH>{}); break;
             }
         }
     }
@@ -411,10 +410,10 @@ __global__ void __launch_bounds__(640) conv_narrow_roll_x3_kernel(const NarrowX3
         for (int s = 0; s < NBLK / 2; ++s) {
             if (q + 2 * s >= nrows + 2) break;
             switch (s) {       // static S0 = (q + 2s) mod 8 for the accumulator rotation
-                case 0: pair_step(q + 0, ICS<0>{}); break;
-                case 1: pair_step(q + 2, ICS<2>{}); break;
-                case 2: pair_step(q + 4, ICS<4>{}); break;
-                default: pair_step(q + 6, ICS<6>{}); break;
+                case 0: pair_step(q + 0, IC<0>{}); break;
+                case 1: pair_step(q + 2, IC<2>{}); break;
+                case 2: pair_step(q + 4, IC<4>{}); break;
+                default: pair_step(q + 6, IC<6>{}); break;
             }
         }
     }
@@ -458,15 +457,7 @@ extern "C" int dl_conv_narrow_forward_x3(const void *x, int N, int H, int W, int
     else if (Cout == 1 && act == DL_ACT_TANH) kern = conv_narrow_roll_x3_kernel<7, 7, 1, DL_ACT_TANH>;
     else if (Cout == 1 && act == DL_ACT_NONE) kern = conv_narrow_roll_x3_kernel<7, 7, 1, DL_ACT_NONE>;
     else DL_FAIL("dl_conv_narrow_forward_x3: Cout=%d / act=%d has no instantiation (Cout 1 or 3, act none or tanh)", Cout, act);
-    static void (*attr_done[4])(const NarrowX3Args) = {nullptr, nullptr, nullptr, nullptr};
-    bool seen = false;
-    for (int i = 0; i < 4; ++i) seen |= attr_done[i] == kern;
-    if (!seen) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-        if (e != hipSuccess) DL_FAIL("dl_conv_narrow_forward_x3: hipFuncSetAttribute: %s", hipGetErrorString(e));
-        for (int i = 0; i < 4; ++i)
-            if (!attr_done[i]) { attr_done[i] = kern; break; }
-    }
+    if (dl_lds_limit(reinterpret_cast<const void *>(kern), smem, "dl_conv_narrow_forward_x3")) return -1;
     hipLaunchKernelGGL(kern, dim3(N * a.strips * a.bands), dim3(640), smem, (hipStream_t)stream, a);
     DL_CHECK_LAUNCH("dl_conv_narrow_forward_x3");
     return 0;
@@ -500,15 +491,7 @@ extern "C" int dl_conv_narrow_forward(const void *x, int N, int H, int W, int Ci
     else if (Cout == 1 && act == DL_ACT_TANH) kern = conv_narrow_roll_kernel<7, 7, 1, DL_ACT_TANH>;
     else if (Cout == 1 && act == DL_ACT_NONE) kern = conv_narrow_roll_kernel<7, 7, 1, DL_ACT_NONE>;
     else DL_FAIL("dl_conv_narrow_forward: Cout=%d / act=%d has no instantiation (Cout 1 or 3, act none or tanh)", Cout, act);
-    static void (*attr_done[4])(const NarrowArgs) = {nullptr, nullptr, nullptr, nullptr};
-    bool seen = false;
-    for (int i = 0; i < 4; ++i) seen |= attr_done[i] == kern;
-    if (!seen) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-        if (e != hipSuccess) DL_FAIL("dl_conv_narrow_forward: hipFuncSetAttribute: %s", hipGetErrorString(e));
-        for (int i = 0; i < 4; ++i)
-            if (!attr_done[i]) { attr_done[i] = kern; break; }
-    }
+    if (dl_lds_limit(reinterpret_cast<const void *>(kern), smem, "dl_conv_narrow_forward")) return -1;
     hipLaunchKernelGGL(kern, dim3(N * a.strips * a.bands), dim3(640), smem, (hipStream_t)stream, a);
     DL_CHECK_LAUNCH("dl_conv_narrow_forward");
     return 0;

@@ -29,13 +29,7 @@
 // through the dead operand LDS, whole NHWC pixel rows of 16 B per lane, fused per-(image, channel) statistics (DPP row sums).
 #include "conv_args.h"
 
-typedef __attribute__((ext_vector_type(16))) float f32x16_t;
-typedef __attribute__((address_space(3))) char lds_char_t;
-typedef __attribute__((address_space(3))) const bf16x8_t lds_frag_t;
-
 __device__ __attribute__((aligned(64))) unsigned char g_w4_zero_page[64];
-
-template <int V> struct W4IC { static constexpr int value = V; };
 
 __device__ __forceinline__ float w4_row16_sum(float v) {
     v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xf, 0xf, false));
@@ -83,7 +77,7 @@ __global__ void __launch_bounds__(256) conv_gemm_w4_kernel(const ConvArgs a) {
     // taps are ordered (kh, kw); dh is constant per kernel row (w4_eligible)
     int dhs[3];
 #pragma unroll
-    for (int k = 0; k < 3; ++k) dhs[k] = (int)(int8_t)(a.taps[3 * k] & 0xff);
+    for (int k = 0; k < 3; ++k) dhs[k] = tap_dh(a.taps[3 * k]);
 
     // ---- staging geometry.  Weights: instruction i of wave w fills buffer rows (w*8 + i)*8 .. +8 (output channels).  Activations: waves 0,1 stage
     // image row 0 of the tile (columns 0-63 / 64-127), waves 2,3 image row 1; instruction i covers 8 pixels.  LDS rows are 128 B = 8 chunks of 16 B;
@@ -217,7 +211,7 @@ __global__ void __launch_bounds__(256) conv_gemm_w4_kernel(const ConvArgs a) {
         constexpr int RBASE = decltype(READSc)::value == 2 ? 8 : 0;      // READS == 2: the reads start at MFMA 8 (second half of a sub-step)
         auto rd = [&](auto K) __attribute__((always_inline)) {           // K-th read of the sub-step: W0 X0 W1 X1 W2 X2 W3 X3
             constexpr int k = decltype(K)::value;
-            read_one(W4IC<(k & 1) ? 4 + (k >> 1) : (k >> 1)>{}, wp, xp, Fn, EFc, xe);
+            read_one(IC<(k & 1) ? 4 + (k >> 1) : (k >> 1)>{}, wp, xp, Fn, EFc, xe);
         };
         auto one = [&](auto MI) __attribute__((always_inline)) {
             constexpr int m = decltype(MI)::value;
@@ -226,18 +220,18 @@ __global__ void __launch_bounds__(256) conv_gemm_w4_kernel(const ConvArgs a) {
                 if constexpr (READS) {
                     constexpr int q = m - RBASE;
                     if constexpr (RBASE == 8) {                      // second half of a sub-step: two reads in each of the shadows 8..11
-                        if constexpr (q >= 0 && q < 4) { rd(W4IC<(q >= 0 && q < 4) ? 2 * q : 0>{}); rd(W4IC<(q >= 0 && q < 4) ? 2 * q + 1 : 0>{}); }
+                        if constexpr (q >= 0 && q < 4) { rd(IC<(q >= 0 && q < 4) ? 2 * q : 0>{}); rd(IC<(q >= 0 && q < 4) ? 2 * q + 1 : 0>{}); }
                     } else if constexpr (SEP) {
-                        if constexpr (q >= 0 && q < 8 && (q & 1) == 0) { rd(W4IC<(q >= 0 && q < 8) ? q : 0>{}); rd(W4IC<(q >= 0 && q < 8) ? q + 1 : 0>{}); }
+                        if constexpr (q >= 0 && q < 8 && (q & 1) == 0) { rd(IC<(q >= 0 && q < 8) ? q : 0>{}); rd(IC<(q >= 0 && q < 8) ? q + 1 : 0>{}); }
                     } else {
-                        if constexpr (q >= 0 && q < 8) rd(W4IC<(q >= 0 && q < 8) ? q : 0>{});
+                        if constexpr (q >= 0 && q < 8) rd(IC<(q >= 0 && q < 8) ? q : 0>{});
                     }
                 }
                 hook(MI);
             }
         };
-        one(W4IC<0>{}); one(W4IC<1>{}); one(W4IC<2>{}); one(W4IC<3>{}); one(W4IC<4>{}); one(W4IC<5>{}); one(W4IC<6>{}); one(W4IC<7>{});
-        one(W4IC<8>{}); one(W4IC<9>{}); one(W4IC<10>{}); one(W4IC<11>{}); one(W4IC<12>{}); one(W4IC<13>{}); one(W4IC<14>{}); one(W4IC<15>{});
+        one(IC<0>{}); one(IC<1>{}); one(IC<2>{}); one(IC<3>{}); one(IC<4>{}); one(IC<5>{}); one(IC<6>{}); one(IC<7>{});
+        one(IC<8>{}); one(IC<9>{}); one(IC<10>{}); one(IC<11>{}); one(IC<12>{}); one(IC<13>{}); one(IC<14>{}); one(IC<15>{});
     };
     // pin the issue order of a range written by mfma_range: per MFMA shadow one MFMA, then its reads / its DMA piece
     auto pin = [&](auto M0c, auto M1c, auto READSc, auto NDc) __attribute__((always_inline)) {
@@ -279,22 +273,22 @@ __global__ void __launch_bounds__(256) conv_gemm_w4_kernel(const ConvArgs a) {
     if (G > 0) {
         bool v0;
         const char *xb0 = x_group_base(0, 0, v0);
-        dma_x(W4IC<0>{}, xb0, v0, 0); dma_x(W4IC<1>{}, xb0, v0, 0); dma_x(W4IC<2>{}, xb0, v0, 0); dma_x(W4IC<3>{}, xb0, v0, 0);
-        dma_x(W4IC<4>{}, xb0, v0, 0); dma_x(W4IC<5>{}, xb0, v0, 0); dma_x(W4IC<6>{}, xb0, v0, 0); dma_x(W4IC<7>{}, xb0, v0, 0);
-        dma_w(W4IC<0>{}, wg, W4IC<0>{}); dma_w(W4IC<1>{}, wg, W4IC<0>{}); dma_w(W4IC<2>{}, wg, W4IC<0>{}); dma_w(W4IC<3>{}, wg, W4IC<0>{});
-        dma_w(W4IC<4>{}, wg, W4IC<0>{}); dma_w(W4IC<5>{}, wg, W4IC<0>{}); dma_w(W4IC<6>{}, wg, W4IC<0>{}); dma_w(W4IC<7>{}, wg, W4IC<0>{});
+        dma_x(IC<0>{}, xb0, v0, 0); dma_x(IC<1>{}, xb0, v0, 0); dma_x(IC<2>{}, xb0, v0, 0); dma_x(IC<3>{}, xb0, v0, 0);
+        dma_x(IC<4>{}, xb0, v0, 0); dma_x(IC<5>{}, xb0, v0, 0); dma_x(IC<6>{}, xb0, v0, 0); dma_x(IC<7>{}, xb0, v0, 0);
+        dma_w(IC<0>{}, wg, IC<0>{}); dma_w(IC<1>{}, wg, IC<0>{}); dma_w(IC<2>{}, wg, IC<0>{}); dma_w(IC<3>{}, wg, IC<0>{});
+        dma_w(IC<4>{}, wg, IC<0>{}); dma_w(IC<5>{}, wg, IC<0>{}); dma_w(IC<6>{}, wg, IC<0>{}); dma_w(IC<7>{}, wg, IC<0>{});
         const char *w1 = wg + tap_bytes;
-        dma_w(W4IC<0>{}, w1, W4IC<1>{}); dma_w(W4IC<1>{}, w1, W4IC<1>{}); dma_w(W4IC<2>{}, w1, W4IC<1>{}); dma_w(W4IC<3>{}, w1, W4IC<1>{});
-        dma_w(W4IC<4>{}, w1, W4IC<1>{}); dma_w(W4IC<5>{}, w1, W4IC<1>{}); dma_w(W4IC<6>{}, w1, W4IC<1>{}); dma_w(W4IC<7>{}, w1, W4IC<1>{});
+        dma_w(IC<0>{}, w1, IC<1>{}); dma_w(IC<1>{}, w1, IC<1>{}); dma_w(IC<2>{}, w1, IC<1>{}); dma_w(IC<3>{}, w1, IC<1>{});
+        dma_w(IC<4>{}, w1, IC<1>{}); dma_w(IC<5>{}, w1, IC<1>{}); dma_w(IC<6>{}, w1, IC<1>{}); dma_w(IC<7>{}, w1, IC<1>{});
         asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
     }
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");          // slab 0, weights 0 visible (weights 1 still in flight: __syncthreads() would drain them)
 
     if (G > 0) {
         const int wp = aw + w4_wofs(0), xp = axk[0], xe = axe[0];
-        constexpr W4IC<(FLIP ? 7 : 4)> EF0{};                              // step 0's slab shift: -1 in the forward order, block 0 holds the off-row pixel
-        read_one(W4IC<0>{}, wp, xp, FA, EF0, xe); read_one(W4IC<4>{}, wp, xp, FA, EF0, xe); read_one(W4IC<1>{}, wp, xp, FA, EF0, xe); read_one(W4IC<5>{}, wp, xp, FA, EF0, xe);
-        read_one(W4IC<2>{}, wp, xp, FA, EF0, xe); read_one(W4IC<6>{}, wp, xp, FA, EF0, xe); read_one(W4IC<3>{}, wp, xp, FA, EF0, xe); read_one(W4IC<7>{}, wp, xp, FA, EF0, xe);
+        constexpr IC<(FLIP ? 7 : 4)> EF0{};                              // step 0's slab shift: -1 in the forward order, block 0 holds the off-row pixel
+        read_one(IC<0>{}, wp, xp, FA, EF0, xe); read_one(IC<4>{}, wp, xp, FA, EF0, xe); read_one(IC<1>{}, wp, xp, FA, EF0, xe); read_one(IC<5>{}, wp, xp, FA, EF0, xe);
+        read_one(IC<2>{}, wp, xp, FA, EF0, xe); read_one(IC<6>{}, wp, xp, FA, EF0, xe); read_one(IC<3>{}, wp, xp, FA, EF0, xe); read_one(IC<7>{}, wp, xp, FA, EF0, xe);
     }
 
     // K step t = 3 g + KW of group g: see the header comment
@@ -317,14 +311,14 @@ __global__ void __launch_bounds__(256) conv_gemm_w4_kernel(const ConvArgs a) {
             constexpr int p = decltype(Pc)::value;
             if constexpr (!DMA_ON) return;
             constexpr int NX = KW < 2 ? 4 : 0;
-            if constexpr (p < NX) dma_x(W4IC<(KW == 1 ? 4 : 0) + (p < NX ? p : 0)>{}, xb_n, xv_n, xslab);
-            else if constexpr (p - NX < 8) dma_w(W4IC<(p - NX >= 0 && p - NX < 8) ? p - NX : 0>{}, wsrc, W4IC<(KW + 2) % 3>{});
+            if constexpr (p < NX) dma_x(IC<(KW == 1 ? 4 : 0) + (p < NX ? p : 0)>{}, xb_n, xv_n, xslab);
+            else if constexpr (p - NX < 8) dma_w(IC<(p - NX >= 0 && p - NX < 8) ? p - NX : 0>{}, wsrc, IC<(KW + 2) % 3>{});
         };
         auto hook_s = [&](auto Sc) __attribute__((always_inline)) {
             return [&](auto MI) __attribute__((always_inline)) {
                 constexpr int s = decltype(Sc)::value, m = decltype(MI)::value;
                 constexpr int k = dma_slot(m);
-                if constexpr (k >= 0) piece(W4IC<(k >= 0 ? s * 4 + k : 0)>{});
+                if constexpr (k >= 0) piece(IC<(k >= 0 ? s * 4 + k : 0)>{});
             };
         };
         constexpr int NP = KW < 2 ? 12 : 8;                               // pieces of this step
@@ -332,35 +326,35 @@ __global__ void __launch_bounds__(256) conv_gemm_w4_kernel(const ConvArgs a) {
         // sched_barrier(0) at every sub-step boundary: without it hipcc hoists the edge fix of the NEXT sub-step's fragment up to the read that
         // fetches it (an s_waitcnt lgkmcnt(0) on a fresh read in the middle of the MFMA stream)
         __builtin_amdgcn_sched_barrier(0);
-        fix_edge(W4IC<SH>{}, FA);
-        mfma_range(W4IC<0>{}, W4IC<16>{}, W4IC<1>{}, FA, FB, wcur ^ (1 << 5), xcur ^ (1 << 5), hook_s(W4IC<0>{}), W4IC<EFC>{}, xecur ^ (1 << 5));
-        pin(W4IC<0>{}, W4IC<16>{}, W4IC<1>{}, W4IC<DMA_ON ? ND0 : 0>{});
+        fix_edge(IC<SH>{}, FA);
+        mfma_range(IC<0>{}, IC<16>{}, IC<1>{}, FA, FB, wcur ^ (1 << 5), xcur ^ (1 << 5), hook_s(IC<0>{}), IC<EFC>{}, xecur ^ (1 << 5));
+        pin(IC<0>{}, IC<16>{}, IC<1>{}, IC<DMA_ON ? ND0 : 0>{});
         __builtin_amdgcn_sched_barrier(0);
-        fix_edge(W4IC<SH>{}, FB);
-        mfma_range(W4IC<0>{}, W4IC<16>{}, W4IC<1>{}, FB, FA, wcur ^ (2 << 5), xcur ^ (2 << 5), hook_s(W4IC<1>{}), W4IC<EFC>{}, xecur ^ (2 << 5));
-        pin(W4IC<0>{}, W4IC<16>{}, W4IC<1>{}, W4IC<DMA_ON ? ND1 : 0>{});
+        fix_edge(IC<SH>{}, FB);
+        mfma_range(IC<0>{}, IC<16>{}, IC<1>{}, FB, FA, wcur ^ (2 << 5), xcur ^ (2 << 5), hook_s(IC<1>{}), IC<EFC>{}, xecur ^ (2 << 5));
+        pin(IC<0>{}, IC<16>{}, IC<1>{}, IC<DMA_ON ? ND1 : 0>{});
         __builtin_amdgcn_sched_barrier(0);
-        fix_edge(W4IC<SH>{}, FA);
-        if constexpr (ND2 > 0) mfma_range(W4IC<0>{}, W4IC<16>{}, W4IC<1>{}, FA, FB, wcur ^ (3 << 5), xcur ^ (3 << 5), hook_s(W4IC<2>{}), W4IC<EFC>{}, xecur ^ (3 << 5));
-        else mfma_range(W4IC<0>{}, W4IC<16>{}, W4IC<1>{}, FA, FB, wcur ^ (3 << 5), xcur ^ (3 << 5), nohook, W4IC<EFC>{}, xecur ^ (3 << 5));
-        pin(W4IC<0>{}, W4IC<16>{}, W4IC<1>{}, W4IC<DMA_ON ? ND2 : 0>{});
+        fix_edge(IC<SH>{}, FA);
+        if constexpr (ND2 > 0) mfma_range(IC<0>{}, IC<16>{}, IC<1>{}, FA, FB, wcur ^ (3 << 5), xcur ^ (3 << 5), hook_s(IC<2>{}), IC<EFC>{}, xecur ^ (3 << 5));
+        else mfma_range(IC<0>{}, IC<16>{}, IC<1>{}, FA, FB, wcur ^ (3 << 5), xcur ^ (3 << 5), nohook, IC<EFC>{}, xecur ^ (3 << 5));
+        pin(IC<0>{}, IC<16>{}, IC<1>{}, IC<DMA_ON ? ND2 : 0>{});
         __builtin_amdgcn_sched_barrier(0);
-        fix_edge(W4IC<SH>{}, FB);
+        fix_edge(IC<SH>{}, FB);
         // everything but the 8 youngest pieces (= W(t+2)) has landed: W(t+1), the slab pieces of this step; this wave's reads of buffer t are complete
         if constexpr (LATE) {
-            mfma_range(W4IC<0>{}, W4IC<8>{}, W4IC<0>{}, FB, FA, wnext, xnext, nohook, W4IC<EFN>{}, xenext);
-            pin(W4IC<0>{}, W4IC<8>{}, W4IC<0>{}, W4IC<0>{});
+            mfma_range(IC<0>{}, IC<8>{}, IC<0>{}, FB, FA, wnext, xnext, nohook, IC<EFN>{}, xenext);
+            pin(IC<0>{}, IC<8>{}, IC<0>{}, IC<0>{});
             __builtin_amdgcn_sched_barrier(0);          // keeps those 8 MFMAs in front of the barrier (register-only instructions may cross an asm)
         }
         if constexpr (ABL == 5) asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
         else if constexpr (DMA_ON) asm volatile("s_waitcnt vmcnt(8) lgkmcnt(0)\n\ts_barrier" ::: "memory");
         else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
         if constexpr (LATE) {
-            mfma_range(W4IC<8>{}, W4IC<16>{}, W4IC<2>{}, FB, FA, wnext, xnext, nohook, W4IC<EFN>{}, xenext);
-            pin(W4IC<8>{}, W4IC<16>{}, W4IC<2>{}, W4IC<0>{});
+            mfma_range(IC<8>{}, IC<16>{}, IC<2>{}, FB, FA, wnext, xnext, nohook, IC<EFN>{}, xenext);
+            pin(IC<8>{}, IC<16>{}, IC<2>{}, IC<0>{});
         } else {
-            mfma_range(W4IC<0>{}, W4IC<16>{}, W4IC<1>{}, FB, FA, wnext, xnext, nohook, W4IC<EFN>{}, xenext);
-            pin(W4IC<0>{}, W4IC<16>{}, W4IC<1>{}, W4IC<0>{});
+            mfma_range(IC<0>{}, IC<16>{}, IC<1>{}, FB, FA, wnext, xnext, nohook, IC<EFN>{}, xenext);
+            pin(IC<0>{}, IC<16>{}, IC<1>{}, IC<0>{});
         }
         (void)SHN;
     };
@@ -368,9 +362,9 @@ __global__ void __launch_bounds__(256) conv_gemm_w4_kernel(const ConvArgs a) {
     for (int g = 0; g < G; ++g) {
         int cn, khn;
         advance(g, cn, khn);
-        step(W4IC<0>{}, g);
-        step(W4IC<1>{}, g);
-        step(W4IC<2>{}, g);
+        step(IC<0>{}, g);
+        step(IC<1>{}, g);
+        step(IC<2>{}, g);
         c = cn; kh = khn; wgrp = wgrp_n;
     }
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
@@ -438,7 +432,7 @@ __global__ void __launch_bounds__(256) conv_gemm_w4_kernel(const ConvArgs a) {
         for (int k = 0; k < 16; ++k)
             pre[k] = *reinterpret_cast<const u32x4_t *>(addp + (size_t)(8 * k) * pps);
     }
-    if (a.act == DL_ACT_RELU) acc_pass(W4IC<1>{}); else acc_pass(W4IC<0>{});
+    if (a.act == DL_ACT_RELU) acc_pass(IC<1>{}); else acc_pass(IC<0>{});
     __syncthreads();
     bf16_t *out = reinterpret_cast<bf16_t *>(a.out);
     // store pass: thread t owns 16-byte chunk t & 31 (channels (t & 31) * 8 ..) of pixel rows (t >> 5) + 8 k.  Two compile-time options:
@@ -507,9 +501,9 @@ __global__ void __launch_bounds__(256) conv_gemm_w4_kernel(const ConvArgs a) {
             }
         }
     };
-    if (want_bn) store_pass(W4IC<0>{}, W4IC<2>{}, pre);
-    else if (want_stats) { if (want_add) store_pass(W4IC<1>{}, W4IC<1>{}, pre); else store_pass(W4IC<0>{}, W4IC<1>{}, pre); }
-    else { if (want_add) store_pass(W4IC<1>{}, W4IC<0>{}, pre); else store_pass(W4IC<0>{}, W4IC<0>{}, pre); }
+    if (want_bn) store_pass(IC<0>{}, IC<2>{}, pre);
+    else if (want_stats) { if (want_add) store_pass(IC<1>{}, IC<1>{}, pre); else store_pass(IC<0>{}, IC<1>{}, pre); }
+    else { if (want_add) store_pass(IC<1>{}, IC<0>{}, pre); else store_pass(IC<0>{}, IC<0>{}, pre); }
     if (want_stats || want_bn) {
         // the 8 threads of a channel group are lanes c, c + 32 of the four waves: one shuffle, then the waves meet in LDS (fixed order: deterministic)
 #pragma unroll
@@ -530,7 +524,7 @@ __global__ void __launch_bounds__(256) conv_gemm_w4_kernel(const ConvArgs a) {
 }
 
 // taps of kernel row 0 ordered dw = +1, 0, -1 (the data gradient's order)?
-static bool w4_flipped(const ConvArgs &a) { return (int8_t)((a.taps[0] >> 8) & 0xff) == 1; }
+static bool w4_flipped(const ConvArgs &a) { return tap_dw(a.taps[0]) == 1; }
 
 // The layers this kernel serves: one phase of 9 taps ordered (kh, kw) with dh constant per kernel row and the SAME dw order (-1, 0, +1 or reversed:
 // the data gradient) in every row, stride 1, image rows exactly 128 pixels wide (a 256-pixel tile = two whole image rows), zero padding (or replicate padding in the forward tap order),
@@ -544,16 +538,15 @@ bool w4_eligible(const ConvArgs &a) {
     if ((size_t)a.Hi * a.Wi * (size_t)a.in_pstride * 2 >= ((size_t)1 << 31) || (size_t)256 * a.w_kstride * 2 >= ((size_t)1 << 31)) return false;   // 32-bit lane offsets
     int seen = 0;
     for (int kh = 0; kh < 3; ++kh) {
-        const int dh0 = (int8_t)(a.taps[kh * 3] & 0xff);
+        const int dh0 = tap_dh(a.taps[kh * 3]);
         if (dh0 < -1 || dh0 > 1) return false;
         for (int kw = 0; kw < 3; ++kw) {
             const int16_t tp = a.taps[kh * 3 + kw];
-            const int dh = (int8_t)(tp & 0xff), dw = (int8_t)((tp >> 8) & 0xff);
-            if (dh != dh0 || dw != (int8_t)((a.taps[kw] >> 8) & 0xff)) return false;
+            if (tap_dh(tp) != dh0 || tap_dw(tp) != tap_dw(a.taps[kw])) return false;
         }
         seen |= 1 << (dh0 + 1);
     }
-    const int d0 = (int8_t)((a.taps[0] >> 8) & 0xff), d1 = (int8_t)((a.taps[1] >> 8) & 0xff), d2 = (int8_t)((a.taps[2] >> 8) & 0xff);
+    const int d0 = tap_dw(a.taps[0]), d1 = tap_dw(a.taps[1]), d2 = tap_dw(a.taps[2]);
     if (!((d0 == -1 && d1 == 0 && d2 == 1) || (d0 == 1 && d1 == 0 && d2 == -1))) return false;
     if (a.pad_mode != DL_PAD_ZERO && d0 != -1) return false;             // a copying border: forward tap order only (conv_gemm_w4_kernel<.., BORDER>)
     return seen == 7;
@@ -562,12 +555,7 @@ bool w4_eligible(const ConvArgs &a) {
 template <bool FLIP, int VAR, int ABL, int BORDER = DL_PAD_ZERO>
 static int launch_w4(const ConvArgs &a, hipStream_t stream) {
     auto kern = conv_gemm_w4_kernel<FLIP, VAR, ABL, BORDER>;
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)W4_LDS);
-        if (e != hipSuccess) DL_FAIL("dl_conv_forward(w4): hipFuncSetAttribute(%zu): %s", W4_LDS, hipGetErrorString(e));
-        attr_set = true;
-    }
+    if (dl_lds_limit(reinterpret_cast<const void *>(kern), W4_LDS, "dl_conv_forward(w4)")) return -1;
     dim3 grid(a.tiles_m * a.tiles_n, 1);
     hipLaunchKernelGGL(kern, grid, dim3(256), W4_LDS, stream, a);
     DL_CHECK_LAUNCH("dl_conv_forward(w4)");

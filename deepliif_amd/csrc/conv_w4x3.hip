@@ -16,12 +16,6 @@
 // copies always stay on the 8-phase kernel.
 #include "conv_args.h"
 
-typedef __attribute__((ext_vector_type(16))) float f32x16_t;
-typedef __attribute__((address_space(3))) char lds_char_t;
-typedef __attribute__((address_space(3))) const bf16x8_t lds_frag_t;
-
-template <int V> struct X4IC { static constexpr int value = V; };
-
 __device__ __forceinline__ float x4_row16_sum(float v) {
     v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xf, 0xf, false));
     v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x4E, 0xf, 0xf, false));
@@ -53,7 +47,7 @@ __global__ void __launch_bounds__(256) conv_gemm_w4x3_kernel(const ConvArgs a) {
 
     int dhs[3];
 #pragma unroll
-    for (int k = 0; k < 3; ++k) dhs[k] = (int)(int8_t)(a.taps[3 * k] & 0xff);
+    for (int k = 0; k < 3; ++k) dhs[k] = tap_dh(a.taps[3 * k]);
 
     // ---- staging geometry (as conv_gemm_w4_kernel): LDS rows are 128 B = 8 chunks of 16 B, chunk c of row r at position c ^ ((r >> 1) & 7)
     const int lrow = lane >> 3, lcp = lane & 7;
@@ -165,17 +159,17 @@ __global__ void __launch_bounds__(256) conv_gemm_w4x3_kernel(const ConvArgs a) {
             constexpr int m = decltype(Mc)::value;
             mma3(Mc, Fc);
             if constexpr (READS && m < 16 && (m & 1) == 0) {
-                read_k(X4IC<(m < 16) ? m : 0>{}, wbase, xbase, wsw, xsw, Fn);
-                read_k(X4IC<(m < 16) ? m + 1 : 0>{}, wbase, xbase, wsw, xsw, Fn);
+                read_k(IC<(m < 16) ? m : 0>{}, wbase, xbase, wsw, xsw, Fn);
+                read_k(IC<(m < 16) ? m + 1 : 0>{}, wbase, xbase, wsw, xsw, Fn);
             }
             hook(Mc);
         };
-        one(X4IC<0>{}); one(X4IC<1>{}); one(X4IC<2>{}); one(X4IC<3>{}); one(X4IC<4>{}); one(X4IC<5>{}); one(X4IC<6>{}); one(X4IC<7>{});
-        one(X4IC<8>{}); one(X4IC<9>{}); one(X4IC<10>{}); one(X4IC<11>{}); one(X4IC<12>{}); one(X4IC<13>{}); one(X4IC<14>{}); one(X4IC<15>{});
-        one(X4IC<16>{}); one(X4IC<17>{}); one(X4IC<18>{}); one(X4IC<19>{}); one(X4IC<20>{}); one(X4IC<21>{}); one(X4IC<22>{}); one(X4IC<23>{});
-        one(X4IC<24>{}); one(X4IC<25>{}); one(X4IC<26>{}); one(X4IC<27>{}); one(X4IC<28>{}); one(X4IC<29>{}); one(X4IC<30>{}); one(X4IC<31>{});
-        one(X4IC<32>{}); one(X4IC<33>{}); one(X4IC<34>{}); one(X4IC<35>{}); one(X4IC<36>{}); one(X4IC<37>{}); one(X4IC<38>{}); one(X4IC<39>{});
-        one(X4IC<40>{}); one(X4IC<41>{}); one(X4IC<42>{}); one(X4IC<43>{}); one(X4IC<44>{}); one(X4IC<45>{}); one(X4IC<46>{}); one(X4IC<47>{});
+        one(IC<0>{}); one(IC<1>{}); one(IC<2>{}); one(IC<3>{}); one(IC<4>{}); one(IC<5>{}); one(IC<6>{}); one(IC<7>{});
+        one(IC<8>{}); one(IC<9>{}); one(IC<10>{}); one(IC<11>{}); one(IC<12>{}); one(IC<13>{}); one(IC<14>{}); one(IC<15>{});
+        one(IC<16>{}); one(IC<17>{}); one(IC<18>{}); one(IC<19>{}); one(IC<20>{}); one(IC<21>{}); one(IC<22>{}); one(IC<23>{});
+        one(IC<24>{}); one(IC<25>{}); one(IC<26>{}); one(IC<27>{}); one(IC<28>{}); one(IC<29>{}); one(IC<30>{}); one(IC<31>{});
+        one(IC<32>{}); one(IC<33>{}); one(IC<34>{}); one(IC<35>{}); one(IC<36>{}); one(IC<37>{}); one(IC<38>{}); one(IC<39>{});
+        one(IC<40>{}); one(IC<41>{}); one(IC<42>{}); one(IC<43>{}); one(IC<44>{}); one(IC<45>{}); one(IC<46>{}); one(IC<47>{});
     };
     auto pin = [&](auto READSc, auto NDc) __attribute__((always_inline)) {
         constexpr bool READS = decltype(READSc)::value != 0;
@@ -206,12 +200,12 @@ __global__ void __launch_bounds__(256) conv_gemm_w4x3_kernel(const ConvArgs a) {
     if (G > 0) {
         bool v0;
         const int xo0 = x_group_off(0, 0, v0);
-        dma_x(X4IC<0>{}, xo0, v0, 0); dma_x(X4IC<1>{}, xo0, v0, 0); dma_x(X4IC<2>{}, xo0, v0, 0); dma_x(X4IC<3>{}, xo0, v0, 0);
-        dma_x(X4IC<4>{}, xo0, v0, 0); dma_x(X4IC<5>{}, xo0, v0, 0); dma_x(X4IC<6>{}, xo0, v0, 0); dma_x(X4IC<7>{}, xo0, v0, 0);
-        dma_w(X4IC<0>{}, 0, X4IC<0>{}); dma_w(X4IC<1>{}, 0, X4IC<0>{}); dma_w(X4IC<2>{}, 0, X4IC<0>{}); dma_w(X4IC<3>{}, 0, X4IC<0>{});
-        dma_w(X4IC<4>{}, 0, X4IC<0>{}); dma_w(X4IC<5>{}, 0, X4IC<0>{}); dma_w(X4IC<6>{}, 0, X4IC<0>{}); dma_w(X4IC<7>{}, 0, X4IC<0>{});
-        dma_w(X4IC<0>{}, tap_bytes, X4IC<1>{}); dma_w(X4IC<1>{}, tap_bytes, X4IC<1>{}); dma_w(X4IC<2>{}, tap_bytes, X4IC<1>{}); dma_w(X4IC<3>{}, tap_bytes, X4IC<1>{});
-        dma_w(X4IC<4>{}, tap_bytes, X4IC<1>{}); dma_w(X4IC<5>{}, tap_bytes, X4IC<1>{}); dma_w(X4IC<6>{}, tap_bytes, X4IC<1>{}); dma_w(X4IC<7>{}, tap_bytes, X4IC<1>{});
+        dma_x(IC<0>{}, xo0, v0, 0); dma_x(IC<1>{}, xo0, v0, 0); dma_x(IC<2>{}, xo0, v0, 0); dma_x(IC<3>{}, xo0, v0, 0);
+        dma_x(IC<4>{}, xo0, v0, 0); dma_x(IC<5>{}, xo0, v0, 0); dma_x(IC<6>{}, xo0, v0, 0); dma_x(IC<7>{}, xo0, v0, 0);
+        dma_w(IC<0>{}, 0, IC<0>{}); dma_w(IC<1>{}, 0, IC<0>{}); dma_w(IC<2>{}, 0, IC<0>{}); dma_w(IC<3>{}, 0, IC<0>{});
+        dma_w(IC<4>{}, 0, IC<0>{}); dma_w(IC<5>{}, 0, IC<0>{}); dma_w(IC<6>{}, 0, IC<0>{}); dma_w(IC<7>{}, 0, IC<0>{});
+        dma_w(IC<0>{}, tap_bytes, IC<1>{}); dma_w(IC<1>{}, tap_bytes, IC<1>{}); dma_w(IC<2>{}, tap_bytes, IC<1>{}); dma_w(IC<3>{}, tap_bytes, IC<1>{});
+        dma_w(IC<4>{}, tap_bytes, IC<1>{}); dma_w(IC<5>{}, tap_bytes, IC<1>{}); dma_w(IC<6>{}, tap_bytes, IC<1>{}); dma_w(IC<7>{}, tap_bytes, IC<1>{});
         asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
     }
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");          // slab 0, weights 0 visible (weights 1 still in flight)
@@ -219,10 +213,10 @@ __global__ void __launch_bounds__(256) conv_gemm_w4x3_kernel(const ConvArgs a) {
     if (G > 0) {
         const int wb = aw_row + x4_wofs(0), xb = ax_row[0];
         const int wsw = w_pos(0), xsw = x_pos_hi(0, 0);
-        read_k(X4IC<0>{}, wb, xb, wsw, xsw, FA); read_k(X4IC<1>{}, wb, xb, wsw, xsw, FA); read_k(X4IC<2>{}, wb, xb, wsw, xsw, FA); read_k(X4IC<3>{}, wb, xb, wsw, xsw, FA);
-        read_k(X4IC<4>{}, wb, xb, wsw, xsw, FA); read_k(X4IC<5>{}, wb, xb, wsw, xsw, FA); read_k(X4IC<6>{}, wb, xb, wsw, xsw, FA); read_k(X4IC<7>{}, wb, xb, wsw, xsw, FA);
-        read_k(X4IC<8>{}, wb, xb, wsw, xsw, FA); read_k(X4IC<9>{}, wb, xb, wsw, xsw, FA); read_k(X4IC<10>{}, wb, xb, wsw, xsw, FA); read_k(X4IC<11>{}, wb, xb, wsw, xsw, FA);
-        read_k(X4IC<12>{}, wb, xb, wsw, xsw, FA); read_k(X4IC<13>{}, wb, xb, wsw, xsw, FA); read_k(X4IC<14>{}, wb, xb, wsw, xsw, FA); read_k(X4IC<15>{}, wb, xb, wsw, xsw, FA);
+        read_k(IC<0>{}, wb, xb, wsw, xsw, FA); read_k(IC<1>{}, wb, xb, wsw, xsw, FA); read_k(IC<2>{}, wb, xb, wsw, xsw, FA); read_k(IC<3>{}, wb, xb, wsw, xsw, FA);
+        read_k(IC<4>{}, wb, xb, wsw, xsw, FA); read_k(IC<5>{}, wb, xb, wsw, xsw, FA); read_k(IC<6>{}, wb, xb, wsw, xsw, FA); read_k(IC<7>{}, wb, xb, wsw, xsw, FA);
+        read_k(IC<8>{}, wb, xb, wsw, xsw, FA); read_k(IC<9>{}, wb, xb, wsw, xsw, FA); read_k(IC<10>{}, wb, xb, wsw, xsw, FA); read_k(IC<11>{}, wb, xb, wsw, xsw, FA);
+        read_k(IC<12>{}, wb, xb, wsw, xsw, FA); read_k(IC<13>{}, wb, xb, wsw, xsw, FA); read_k(IC<14>{}, wb, xb, wsw, xsw, FA); read_k(IC<15>{}, wb, xb, wsw, xsw, FA);
     }
 
     // K step t = 3 g + KW of group g (32 channels of one tap): sub-step 0 carries the DMA of step t+2 and the reads of sub-step 1; barrier; sub-step 1
@@ -241,32 +235,32 @@ __global__ void __launch_bounds__(256) conv_gemm_w4x3_kernel(const ConvArgs a) {
             constexpr int p = decltype(Pc)::value;
             if constexpr (!DMA_ON) return;
             constexpr int NX = KW < 2 ? 4 : 0;
-            if constexpr (p < NX) dma_x(X4IC<(KW == 1 ? 4 : 0) + (p < NX ? p : 0)>{}, xo_n, xv_n, xslab);
-            else if constexpr (p - NX < 8) dma_w(X4IC<(p - NX >= 0 && p - NX < 8) ? p - NX : 0>{}, wsrc, X4IC<(KW + 2) % 3>{});
+            if constexpr (p < NX) dma_x(IC<(KW == 1 ? 4 : 0) + (p < NX ? p : 0)>{}, xo_n, xv_n, xslab);
+            else if constexpr (p - NX < 8) dma_w(IC<(p - NX >= 0 && p - NX < 8) ? p - NX : 0>{}, wsrc, IC<(KW + 2) % 3>{});
         };
         constexpr int NP = KW < 2 ? 12 : 8;
         auto hook = [&](auto Mc) __attribute__((always_inline)) {
             constexpr int m = decltype(Mc)::value;
-            if constexpr ((m & 1) == 1 && (m >> 1) < NP) piece(X4IC<((m & 1) == 1 && (m >> 1) < NP) ? (m >> 1) : 0>{});
+            if constexpr ((m & 1) == 1 && (m >> 1) < NP) piece(IC<((m & 1) == 1 && (m >> 1) < NP) ? (m >> 1) : 0>{});
         };
         __builtin_amdgcn_sched_barrier(0);
-        fix_edge(X4IC<SH>{}, FA);
-        substep(X4IC<1>{}, FA, FB, wcur, xcur, w_pos(1), x_pos_hi(1, KW), hook);
-        pin(X4IC<1>{}, X4IC<DMA_ON ? NP : 0>{});
+        fix_edge(IC<SH>{}, FA);
+        substep(IC<1>{}, FA, FB, wcur, xcur, w_pos(1), x_pos_hi(1, KW), hook);
+        pin(IC<1>{}, IC<DMA_ON ? NP : 0>{});
         __builtin_amdgcn_sched_barrier(0);
-        fix_edge(X4IC<SH>{}, FB);
+        fix_edge(IC<SH>{}, FB);
         if constexpr (DMA_ON) asm volatile("s_waitcnt vmcnt(8) lgkmcnt(0)\n\ts_barrier" ::: "memory");
         else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-        substep(X4IC<1>{}, FB, FA, wnext, xnext, w_pos(0), xsw_next, nohook);
-        pin(X4IC<1>{}, X4IC<0>{});
+        substep(IC<1>{}, FB, FA, wnext, xnext, w_pos(0), xsw_next, nohook);
+        pin(IC<1>{}, IC<0>{});
     };
 
     for (int g = 0; g < G; ++g) {
         int cn, khn;
         advance(g, cn, khn);
-        step(X4IC<0>{}, g);
-        step(X4IC<1>{}, g);
-        step(X4IC<2>{}, g);
+        step(IC<0>{}, g);
+        step(IC<1>{}, g);
+        step(IC<2>{}, g);
         c = cn; kh = khn; wgrp = wgrp_n;
     }
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
@@ -349,7 +343,7 @@ __global__ void __launch_bounds__(256) conv_gemm_w4x3_kernel(const ConvArgs a) {
     }
 }
 
-static bool w4x3_flipped(const ConvArgs &a) { return (int8_t)((a.taps[0] >> 8) & 0xff) == 1; }
+static bool w4x3_flipped(const ConvArgs &a) { return tap_dw(a.taps[0]) == 1; }
 
 // The layers this kernel serves: conv_gemm_w4_kernel's (w4_eligible, conv_w4.hip) under the strict policy, with a SPLIT-COPY input, Cin a multiple of 32
 bool w4x3_eligible(const ConvArgs &a) {
@@ -363,16 +357,15 @@ bool w4x3_eligible(const ConvArgs &a) {
     if ((size_t)(a.Hi + 2) * a.Wi * (size_t)a.in_pstride * 4 >= ((size_t)1 << 31)) return false;          // 32-bit lane / scalar offsets
     int seen = 0;
     for (int kh = 0; kh < 3; ++kh) {
-        const int dh0 = (int8_t)(a.taps[kh * 3] & 0xff);
+        const int dh0 = tap_dh(a.taps[kh * 3]);
         if (dh0 < -1 || dh0 > 1) return false;
         for (int kw = 0; kw < 3; ++kw) {
             const int16_t tp = a.taps[kh * 3 + kw];
-            const int dh = (int8_t)(tp & 0xff), dw = (int8_t)((tp >> 8) & 0xff);
-            if (dh != dh0 || dw != (int8_t)((a.taps[kw] >> 8) & 0xff)) return false;
+            if (tap_dh(tp) != dh0 || tap_dw(tp) != tap_dw(a.taps[kw])) return false;
         }
         seen |= 1 << (dh0 + 1);
     }
-    const int d0 = (int8_t)((a.taps[0] >> 8) & 0xff), d1 = (int8_t)((a.taps[1] >> 8) & 0xff), d2 = (int8_t)((a.taps[2] >> 8) & 0xff);
+    const int d0 = tap_dw(a.taps[0]), d1 = tap_dw(a.taps[1]), d2 = tap_dw(a.taps[2]);
     if (!((d0 == -1 && d1 == 0 && d2 == 1) || (d0 == 1 && d1 == 0 && d2 == -1))) return false;
     return seen == 7;
 }
@@ -380,12 +373,7 @@ bool w4x3_eligible(const ConvArgs &a) {
 template <bool FLIP, int ABL>
 static int launch_w4x3(const ConvArgs &a, hipStream_t stream) {
     auto kern = conv_gemm_w4x3_kernel<FLIP, ABL>;
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)X4_LDS);
-        if (e != hipSuccess) DL_FAIL("dl_conv_forward(w4x3): hipFuncSetAttribute(%zu): %s", X4_LDS, hipGetErrorString(e));
-        attr_set = true;
-    }
+    if (dl_lds_limit(reinterpret_cast<const void *>(kern), X4_LDS, "dl_conv_forward(w4x3)")) return -1;
     dim3 grid(a.tiles_m * a.tiles_n, 1);
     hipLaunchKernelGGL(kern, grid, dim3(256), X4_LDS, stream, a);
     DL_CHECK_LAUNCH("dl_conv_forward(w4x3)");

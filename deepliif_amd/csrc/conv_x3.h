@@ -192,7 +192,7 @@ __global__ void __launch_bounds__(512) conv_gemm_8ph_x3_kernel(const ConvArgs a)
 
     if (tid < DL_MAX_TAPS) {
         const int16_t tp = a.taps[tid];
-        tapd_lds[tid] = ((int)(int8_t)(tp & 0xff) * a.Wi + (int)(int8_t)((tp >> 8) & 0xff)) * a.in_pstride;
+        tapd_lds[tid] = (tap_dh(tp) * a.Wi + tap_dw(tp)) * a.in_pstride;
     }
 
     const float *in = reinterpret_cast<const float *>(a.in);
@@ -222,7 +222,7 @@ __global__ void __launch_bounds__(512) conv_gemm_8ph_x3_kernel(const ConvArgs a)
                 if (ok)
                     for (int t = 0; t < ntaps; ++t) {
                         const int16_t tp = a.taps[tap0 + t];
-                        const int hi = hi0 + (int)(int8_t)(tp & 0xff), wi = wi0 + (int)(int8_t)((tp >> 8) & 0xff);
+                        const int hi = hi0 + tap_dh(tp), wi = wi0 + tap_dw(tp);
                         if (((unsigned)hi < (unsigned)a.Hi) && ((unsigned)wi < (unsigned)a.Wi)) mk |= 1ull << t;
                     }
                 x_mask[h][i] = mk;
@@ -538,12 +538,7 @@ static int launch_conv_8ph_x3(const ConvArgs &a0, hipStream_t stream) {
     a.k_order8 = (korder && korder[0] == '0') ? 0 : 1;
     constexpr size_t smem = (size_t)8 * 128 * 128 + DL_MAX_TAPS * sizeof(int);
     auto kern = conv_gemm_8ph_x3_kernel<IN_ACT, ABL, VAR>;
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-        if (e != hipSuccess) DL_FAIL("dl_conv_forward: hipFuncSetAttribute(%zu): %s", smem, hipGetErrorString(e));
-        attr_set = true;
-    }
+    if (dl_lds_limit(reinterpret_cast<const void *>(kern), smem, "dl_conv_forward")) return -1;
     dim3 grid(a.tiles_m * a.tiles_n, a.n_phase * a.splitk);
     hipLaunchKernelGGL(kern, grid, dim3(512), smem, stream, a);
     DL_CHECK_LAUNCH("dl_conv_forward(8-phase x3)");
@@ -588,7 +583,7 @@ __global__ void __launch_bounds__(WM * WN * 64) conv_gemm_glds_x3_kernel(const C
     if (tid < DL_MAX_TAPS) {
         const int16_t tp = a.taps[tid];
         tap_lds[tid] = tp;
-        tapd_lds[tid] = ((int)(int8_t)(tp & 0xff) * a.Wi + (int)(int8_t)((tp >> 8) & 0xff)) * a.in_pstride;
+        tapd_lds[tid] = (tap_dh(tp) * a.Wi + tap_dw(tp)) * a.in_pstride;
     }
 
     const float *in = reinterpret_cast<const float *>(a.in);
@@ -616,7 +611,7 @@ __global__ void __launch_bounds__(WM * WN * 64) conv_gemm_glds_x3_kernel(const C
         if (UTAP && x_ok[i]) {
             for (int t = 0; t < ntaps; ++t) {
                 const int16_t tp = a.taps[tap0 + t];
-                const int hi = x_hi0[i] + (int)(int8_t)(tp & 0xff), wi = x_wi0[i] + (int)(int8_t)((tp >> 8) & 0xff);
+                const int hi = x_hi0[i] + tap_dh(tp), wi = x_wi0[i] + tap_dw(tp);
                 if (((unsigned)hi < (unsigned)a.Hi) && ((unsigned)wi < (unsigned)a.Wi)) mk |= 1ull << t;
             }
         }
@@ -664,7 +659,7 @@ __global__ void __launch_bounds__(WM * WN * 64) conv_gemm_glds_x3_kernel(const C
                     const int ci = k0 & (a.Ci - 1);
                     const int tli = tl < ntaps ? tl : 0;
                     const int16_t t = tap_lds[tap0 + tli];
-                    const int dh = (int)(int8_t)(t & 0xff), dw = (int)(int8_t)((t >> 8) & 0xff);
+                    const int dh = tap_dh(t), dw = tap_dw(t);
                     int hi = x_hi0[i] + dh, wi = x_wi0[i] + dw;
                     if (a.pad_mode != DL_PAD_ZERO) { hi = border_idx(a.pad_mode, hi, a.Hi); wi = border_idx(a.pad_mode, wi, a.Wi); }
                     const bool ok = x_ok[i] && (tl < ntaps) && ((unsigned)hi < (unsigned)a.Hi) && ((unsigned)wi < (unsigned)a.Wi);
@@ -757,12 +752,7 @@ static int launch_conv_glds_x3_impl(const ConvArgs &a0, hipStream_t stream) {
     a.tiles_n = (a.Co + BN - 1) / BN;
     constexpr size_t smem = (size_t)2 * (BM + BN) * 128 + DL_MAX_TAPS * (sizeof(int16_t) + sizeof(int));
     auto kern = conv_gemm_glds_x3_kernel<BM, BN, WM, WN, UTAP, IN_ACT>;
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-        if (e != hipSuccess) DL_FAIL("dl_conv_forward: hipFuncSetAttribute(%zu): %s", smem, hipGetErrorString(e));
-        attr_set = true;
-    }
+    if (dl_lds_limit(reinterpret_cast<const void *>(kern), smem, "dl_conv_forward")) return -1;
     dim3 grid(a.tiles_m * a.tiles_n, a.n_phase * a.splitk);
     hipLaunchKernelGGL(kern, grid, dim3(WM * WN * 64), smem, stream, a);
     DL_CHECK_LAUNCH("dl_conv_forward(glds x3)");

@@ -1,8 +1,13 @@
-// error.cpp -- thread-local last-error string, version, and the load-time table of runtime switches (see include/deepliif_hip.h)
+// error.cpp -- the library's process-wide state: thread-local last-error string, version, the per-device dynamic-LDS grants, and the load-time table of
+// runtime switches (see include/deepliif_hip.h)
+#include <hip/hip_runtime.h>
 #include <stdarg.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <map>
+#include <mutex>
+#include <utility>
 #include "../../include/deepliif_hip.h"
 #include "switches.h"
 
@@ -16,6 +21,27 @@ void dl_set_error(const char *fmt, ...) {
 }
 
 extern "C" const char *dl_last_error(void) { return g_err; }
+
+// ---- the dynamic-LDS grant (common.h).  hipFuncAttributeMaxDynamicSharedMemorySize belongs to a kernel ON A DEVICE, and operands may live on any
+// device of the process (the caller makes theirs current before it launches), so what has been granted is remembered per (device, kernel) -- a flag per
+// launcher would skip the grant on the second device and fail at launch there.  One mutex covers the lookup and the ask: a pair is granted before any
+// caller returns from it, and two threads never ask for the same thing twice.  A hit costs hipGetDevice and one find; only a first grant allocates.
+static std::mutex g_lds_mutex;
+static auto &g_lds_granted = *new std::map<std::pair<int, const void *>, size_t>;       // never destroyed: a thread may still launch while the process exits
+
+int dl_lds_limit(const void *kern, size_t bytes, const char *who) {
+    int dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess) { dl_set_error("%s: hipGetDevice: %s", who, hipGetErrorString(e)); return -1; }
+    std::lock_guard<std::mutex> lock(g_lds_mutex);
+    const auto it = g_lds_granted.find({dev, kern});
+    if (it != g_lds_granted.end() && it->second >= bytes) return 0;
+    e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    if (e != hipSuccess) { dl_set_error("%s: hipFuncSetAttribute(%zu): %s", who, bytes, hipGetErrorString(e)); return -1; }
+    if (it != g_lds_granted.end()) it->second = bytes;
+    else g_lds_granted.emplace(std::make_pair(dev, kern), bytes);
+    return 0;
+}
 extern "C" int dl_version(void) { return DL_VERSION; }
 
 // ---- runtime switches: the variables below are copied out of the environment when the library is loaded; launches only read the copies

@@ -404,10 +404,8 @@ extern "C" int dl_swd_distance(const double *a, const double *b, long long R, co
     if (rt == 1) {
         while (Rp < R) Rp <<= 1;
         lds = ((size_t)2 * Rp + SW_SORT_THREADS) * sizeof(double);                          // at most 139 264 bytes
-        if (lds > (size_t)64 << 10) {                     // above 64 KiB the dynamic LDS of a kernel has to be granted (per device: asked every time)
-            const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(sw_sort_lds_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e != hipSuccess) DL_FAIL("dl_swd_distance: hipFuncSetAttribute(%zu): %s", lds, hipGetErrorString(e));
-        }
+        // above 64 KiB the dynamic LDS of a kernel has to be granted (per device; the size varies with R: a smaller one after a larger asks nothing)
+        if (lds > (size_t)64 << 10 && dl_lds_limit(reinterpret_cast<const void *>(sw_sort_lds_kernel), lds, "dl_swd_distance")) return -1;
     } else {
         hipLaunchKernelGGL(sw_offsets_kernel, dim3((2 * l.pc + 256) / 256), dim3(256), 0, stream, off, 2 * l.pc, (int)R);
     }

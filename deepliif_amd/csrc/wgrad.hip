@@ -50,15 +50,6 @@ static void wgrad_pixel_steps(WgradArgs &a, int bp) {
     a.dn = bp / hw; a.dh = (bp % hw) / a.Wp; a.dw = (bp % hw) % a.Wp;
 }
 
-// raises a kernel's dynamic-LDS limit, once (`done`: the launcher's own static flag, one per kernel instance)
-static int wgrad_lds_limit(const void *kern, size_t smem, bool *done, const char *who) {
-    if (*done) return 0;
-    const hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    if (e != hipSuccess) DL_FAIL("%s: hipFuncSetAttribute(%zu): %s", who, smem, hipGetErrorString(e));
-    *done = true;
-    return 0;
-}
-
 template <typename T> struct RawW;
 template <> struct RawW<bf16_t> { u32x4_t v; };
 template <> struct RawW<float> { f32x4_t a, b; };
@@ -504,7 +495,6 @@ __global__ void __launch_bounds__(512) wgrad_glds_kernel(const WgradArgs a, cons
 //               3            P(H1) upper: 4                             H0 of step t+2 (this buffer);   vmcnt(8): H0(t+1) has landed
 // ------------------------------------------------------------------------------------------------------------------
 #define DL_WBAR() asm volatile("s_barrier" ::: "memory")
-template <int V> struct IC { static constexpr int value = V; };
 __global__ void __launch_bounds__(512) wgrad_8ph_kernel(const WgradArgs a) {
     constexpr int BA = 256, BJ = 256, BP = 64, HP = 32;
     constexpr int ROWA = BA * 2, ROWJ = BJ * 2;             // row bytes
@@ -701,8 +691,7 @@ static int launch_wgrad_8ph(WgradArgs a, hipStream_t stream) {
     a.tiles_a = a.CAp / 256;
     a.tiles_j = (a.J + 255) / 256;
     wgrad_pixel_steps(a, 64);
-    static bool attr_set = false;
-    if (wgrad_lds_limit(reinterpret_cast<const void *>(wgrad_8ph_kernel), smem, &attr_set, "dl_conv_wgrad(8-phase)")) return -1;
+    if (dl_lds_limit(reinterpret_cast<const void *>(wgrad_8ph_kernel), smem, "dl_conv_wgrad(8-phase)")) return -1;
     hipLaunchKernelGGL(wgrad_8ph_kernel, dim3(a.tiles_a * a.tiles_j, a.splitk), dim3(512), smem, stream, a);
     DL_CHECK_LAUNCH("dl_conv_wgrad(8-phase)");
     return 0;
@@ -715,8 +704,7 @@ static int launch_wgrad_glds_v(WgradArgs a, const WgradLayers &lay, int n, hipSt
     a.tiles_j = (a.J + 255) / 256;
     wgrad_pixel_steps(a, 64);
     auto kern = wgrad_glds_kernel<BA, WA, WJ, TRASM>;
-    static bool attr_set = false;
-    if (wgrad_lds_limit(reinterpret_cast<const void *>(kern), smem, &attr_set, "dl_conv_wgrad(glds)")) return -1;
+    if (dl_lds_limit(reinterpret_cast<const void *>(kern), smem, "dl_conv_wgrad(glds)")) return -1;
     hipLaunchKernelGGL(kern, dim3(a.tiles_a * a.tiles_j, a.splitk, n), dim3(512), smem, stream, a, lay);
     DL_CHECK_LAUNCH("dl_conv_wgrad(glds)");
     return 0;
@@ -845,8 +833,7 @@ static int launch_wgrad(WgradArgs a, hipStream_t stream) {
     a.tiles_a = (a.CAp + BA - 1) / BA;
     a.tiles_j = (a.J + 127) / 128;
     auto kern = wgrad_kernel<T, PREC, BA, WA, WJ>;
-    static bool attr_set = false;
-    if (wgrad_lds_limit(reinterpret_cast<const void *>(kern), smem, &attr_set, "dl_conv_wgrad")) return -1;
+    if (dl_lds_limit(reinterpret_cast<const void *>(kern), smem, "dl_conv_wgrad")) return -1;
     hipLaunchKernelGGL(kern, dim3(a.tiles_a * a.tiles_j, a.splitk), dim3(256), smem, stream, a);
     DL_CHECK_LAUNCH("dl_conv_wgrad");
     return 0;

@@ -31,8 +31,6 @@ struct WgradW4Args {
     int tiles_a, tiles_b;        // CAp / 128, CBp / 128
 };
 
-template <int V> struct W4WIC { static constexpr int value = V; };
-
 constexpr int W4W_DY = 128 * 256;                    // bytes of a dy buffer
 constexpr int W4W_X = 130 * 256;                     // bytes of an x buffer (pixel rows -1 .. 128)
 constexpr int W4W_X0 = 2 * W4W_DY;
@@ -119,8 +117,8 @@ __global__ void __launch_bounds__(256) wgrad_w4_kernel(const WgradW4Args a, cons
     // piece k (0..15) of a row: dy pieces and x pieces alternate
     auto piece = [&](auto Kc) __attribute__((always_inline)) {
         constexpr int k = decltype(Kc)::value;
-        if constexpr ((k & 1) == 0) dma_p(W4WIC<(k >> 1)>{});
-        else dma_q(W4WIC<(k >> 1)>{});
+        if constexpr ((k & 1) == 0) dma_p(IC<(k >> 1)>{});
+        else dma_q(IC<(k >> 1)>{});
     };
 
     // ---- fragment addressing (bytes).  lane = 16 g + m: channel 16 (g & 1) + m of a 32-channel block, pixels 8 (g >> 1) + {0..3 | 4..7}; the
@@ -181,22 +179,22 @@ __global__ void __launch_bounds__(256) wgrad_w4_kernel(const WgradW4Args a, cons
             constexpr int q = decltype(Qc)::value;
             mma_one(Qc, Fc);
             if constexpr (q < 7) read_frag(Qc, OFS, Fn);
-            if constexpr (D0 >= 0 && q >= 7 && q < 11) piece(W4WIC<(D0 >= 0 && q >= 7 && q < 11) ? D0 + q - 7 : 0>{});
+            if constexpr (D0 >= 0 && q >= 7 && q < 11) piece(IC<(D0 >= 0 && q >= 7 && q < 11) ? D0 + q - 7 : 0>{});
             if constexpr (COPY && D0 == 12 && q == 11) dma_edge();            // behind the row's last regular piece
             __builtin_amdgcn_sched_barrier(0);
         };
-        one(W4WIC<0>{}); one(W4WIC<1>{}); one(W4WIC<2>{}); one(W4WIC<3>{}); one(W4WIC<4>{}); one(W4WIC<5>{});
-        one(W4WIC<6>{}); one(W4WIC<7>{}); one(W4WIC<8>{}); one(W4WIC<9>{}); one(W4WIC<10>{}); one(W4WIC<11>{});
+        one(IC<0>{}); one(IC<1>{}); one(IC<2>{}); one(IC<3>{}); one(IC<4>{}); one(IC<5>{});
+        one(IC<6>{}); one(IC<7>{}); one(IC<8>{}); one(IC<9>{}); one(IC<10>{}); one(IC<11>{});
     };
     // one K step = one image row (fragments of its sub-step 0 are in FA); the row set_row() named is staged into the other buffer meanwhile
     auto step = [&]() __attribute__((always_inline)) {
-        substep(FA, FB, W4WIC<1 * 4096>{}, W4WIC<0>{});
-        substep(FB, FA, W4WIC<2 * 4096>{}, W4WIC<4>{});
-        substep(FA, FB, W4WIC<3 * 4096>{}, W4WIC<8>{});
-        substep(FB, FA, W4WIC<4 * 4096>{}, W4WIC<12>{});
-        substep(FA, FB, W4WIC<5 * 4096>{}, W4WIC<-1>{});
-        substep(FB, FA, W4WIC<6 * 4096>{}, W4WIC<-1>{});
-        substep(FA, FB, W4WIC<7 * 4096>{}, W4WIC<-1>{});
+        substep(FA, FB, IC<1 * 4096>{}, IC<0>{});
+        substep(FB, FA, IC<2 * 4096>{}, IC<4>{});
+        substep(FA, FB, IC<3 * 4096>{}, IC<8>{});
+        substep(FB, FA, IC<4 * 4096>{}, IC<12>{});
+        substep(FA, FB, IC<5 * 4096>{}, IC<-1>{});
+        substep(FB, FA, IC<6 * 4096>{}, IC<-1>{});
+        substep(FA, FB, IC<7 * 4096>{}, IC<-1>{});
         __builtin_amdgcn_sched_barrier(0);
         // the next row has landed (this wave's pieces; the barrier collects the others') and this wave's reads of the current buffer are complete
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
@@ -206,7 +204,7 @@ __global__ void __launch_bounds__(256) wgrad_w4_kernel(const WgradW4Args a, cons
         for (int k = 0; k < 3; ++k) x_addr[k] += dx;
         da = -da; dx = -dx;
         nb_dy = W4W_DY - nb_dy; nb_x = W4W_X - nb_x;
-        substep(FB, FA, W4WIC<0>{}, W4WIC<-1>{});
+        substep(FB, FA, IC<0>{}, IC<-1>{});
     };
 
     // ---- prologue: padding columns of both x buffers (COPY: staged with every row), first row into buffer 0
@@ -224,14 +222,14 @@ __global__ void __launch_bounds__(256) wgrad_w4_kernel(const WgradW4Args a, cons
     if (nrows > 0) {
         set_row(r);
         if constexpr (COPY) dma_edge();
-        piece(W4WIC<0>{}); piece(W4WIC<1>{}); piece(W4WIC<2>{}); piece(W4WIC<3>{}); piece(W4WIC<4>{}); piece(W4WIC<5>{}); piece(W4WIC<6>{}); piece(W4WIC<7>{});
-        piece(W4WIC<8>{}); piece(W4WIC<9>{}); piece(W4WIC<10>{}); piece(W4WIC<11>{}); piece(W4WIC<12>{}); piece(W4WIC<13>{}); piece(W4WIC<14>{}); piece(W4WIC<15>{});
+        piece(IC<0>{}); piece(IC<1>{}); piece(IC<2>{}); piece(IC<3>{}); piece(IC<4>{}); piece(IC<5>{}); piece(IC<6>{}); piece(IC<7>{});
+        piece(IC<8>{}); piece(IC<9>{}); piece(IC<10>{}); piece(IC<11>{}); piece(IC<12>{}); piece(IC<13>{}); piece(IC<14>{}); piece(IC<15>{});
     }
     nb_dy = W4W_DY; nb_x = W4W_X;
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
     if (nrows > 0) {
-        read_frag(W4WIC<0>{}, W4WIC<0>{}, FA); read_frag(W4WIC<1>{}, W4WIC<0>{}, FA); read_frag(W4WIC<2>{}, W4WIC<0>{}, FA); read_frag(W4WIC<3>{}, W4WIC<0>{}, FA);
-        read_frag(W4WIC<4>{}, W4WIC<0>{}, FA); read_frag(W4WIC<5>{}, W4WIC<0>{}, FA); read_frag(W4WIC<6>{}, W4WIC<0>{}, FA);
+        read_frag(IC<0>{}, IC<0>{}, FA); read_frag(IC<1>{}, IC<0>{}, FA); read_frag(IC<2>{}, IC<0>{}, FA); read_frag(IC<3>{}, IC<0>{}, FA);
+        read_frag(IC<4>{}, IC<0>{}, FA); read_frag(IC<5>{}, IC<0>{}, FA); read_frag(IC<6>{}, IC<0>{}, FA);
         // past the end the last row is staged once more into the idle buffer (no branch around the DMA)
         for (int t = 0; t < nrows; ++t) {
             const int rn = COPY ? (r + 1 < r_end ? r + 1 : -1) : next_valid(r + 1);
@@ -264,10 +262,8 @@ static int launch_wgrad_w4(const dl_wgrad_desc *d, const WgradLayers &lay, int n
     a.p_pstride = d->p_pstride; a.q_pstride = d->q_pstride;
     a.splitk = d->splitk; a.rps = (a.NH + d->splitk - 1) / d->splitk;
     a.tiles_a = d->CAp / 128; a.tiles_b = d->CBp / 128;
-    const bool copy = d->pad_mode == DL_PAD_REPLICATE;
-    auto kern = copy ? wgrad_w4_kernel<DL_PAD_REPLICATE> : wgrad_w4_kernel<DL_PAD_ZERO>;
-    static bool attr_set[2] = {false, false};
-    if (wgrad_lds_limit(reinterpret_cast<const void *>(kern), W4W_LDS, &attr_set[copy], "dl_conv_wgrad(w4)")) return -1;
+    auto kern = d->pad_mode == DL_PAD_REPLICATE ? wgrad_w4_kernel<DL_PAD_REPLICATE> : wgrad_w4_kernel<DL_PAD_ZERO>;
+    if (dl_lds_limit(reinterpret_cast<const void *>(kern), W4W_LDS, "dl_conv_wgrad(w4)")) return -1;
     const int grid = a.tiles_a * a.tiles_b * 3 * a.splitk * n;
     hipLaunchKernelGGL(kern, dim3(grid), dim3(256), W4W_LDS, stream, a, lay);
     DL_CHECK_LAUNCH("dl_conv_wgrad(w4)");

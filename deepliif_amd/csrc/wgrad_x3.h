@@ -511,8 +511,7 @@ static int launch_wgrad_4ph_x3(WgradArgs a, hipStream_t stream) {
     a.tiles_j = (a.J + 255) / 256;
     wgrad_pixel_steps(a, 32);
     auto kern = wgrad_4ph_x3_kernel<NOPRIO>;
-    static bool attr_set = false;
-    if (wgrad_lds_limit(reinterpret_cast<const void *>(kern), smem, &attr_set, "dl_conv_wgrad(4-phase x3)")) return -1;
+    if (dl_lds_limit(reinterpret_cast<const void *>(kern), smem, "dl_conv_wgrad(4-phase x3)")) return -1;
     hipLaunchKernelGGL(kern, dim3(a.tiles_a * a.tiles_j, a.splitk), dim3(512), smem, stream, a);
     DL_CHECK_LAUNCH("dl_conv_wgrad(4-phase x3)");
     return 0;
@@ -525,8 +524,7 @@ static int launch_wgrad_glds_x3_v(WgradArgs a, const WgradLayers &lay, int n, hi
     a.tiles_j = (a.J + 255) / 256;
     wgrad_pixel_steps(a, 32);
     auto kern = wgrad_glds_x3_kernel<BA, TRASM>;
-    static bool attr_set = false;
-    if (wgrad_lds_limit(reinterpret_cast<const void *>(kern), smem, &attr_set, "dl_conv_wgrad(glds x3)")) return -1;
+    if (dl_lds_limit(reinterpret_cast<const void *>(kern), smem, "dl_conv_wgrad(glds x3)")) return -1;
     hipLaunchKernelGGL(kern, dim3(a.tiles_a * a.tiles_j, a.splitk, n), dim3(512), smem, stream, a, lay);
     DL_CHECK_LAUNCH("dl_conv_wgrad(glds x3)");
     return 0;
@@ -676,8 +674,7 @@ static int launch_wgrad_c4_x3(const dl_wgrad_desc *d, int form, const void *P, c
     const int ntiles = a.N * a.tiles_w * a.tiles_h;
     const int parts = ntiles < DL_WGRAD_C4_PARTS ? ntiles : DL_WGRAD_C4_PARTS;
     constexpr size_t smem = (size_t)(2 * 2 * 64 * 80 + 2 * (8 * 72 * 4 + 32)) * sizeof(bf16_t);
-    static bool attr_set = false;
-    if (wgrad_lds_limit(reinterpret_cast<const void *>(wgrad_c4_x3_kernel), smem, &attr_set, "dl_conv_wgrad(c4 x3)")) return -1;
+    if (dl_lds_limit(reinterpret_cast<const void *>(wgrad_c4_x3_kernel), smem, "dl_conv_wgrad(c4 x3)")) return -1;
     hipLaunchKernelGGL(wgrad_c4_x3_kernel, dim3(parts), dim3(256), smem, stream, a);
     DL_CHECK_LAUNCH("dl_conv_wgrad(c4 x3)");
     hipLaunchKernelGGL(wgrad_c4_reduce_kernel, dim3(64 * 56 / 8), dim3(256), 0, stream, slab, parts, grad, d->CA, d->CB, form == 1 ? 1 : 0, d->accumulate);

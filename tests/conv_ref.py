@@ -20,7 +20,7 @@ wave*32 + q*8 + lh*4 + e of pixel j*32 + lr) -- by (wave, lane >= 16, accumulato
 accumulator-to-(pixel, channel) map down as one formula and this file does not guess it: their lane groups show up in the pixel-mod-32 and channel-mod-32
 residues, which are reported for every kernel; conv_dot uses no MFMA.
 
-strip_rows(): a restatement of the four *_strip_rows rules of csrc/conv_{s2d,s2u,d1,d1g}.hip; used as a coverage guard only (the sweep asserts which strip
+strip_rows(): a restatement of strip_rows() of csrc/conv_args.h as csrc/conv_{s2d,s2u,d1,d1g}.hip call it; used as a coverage guard only (the sweep asserts which strip
 heights its table exercises) and cross-checked against the library through dl_conv_stats_chunks (tests/test_dispatch_host.py)."""
 import torch
 import torch.nn.functional as F
@@ -99,7 +99,7 @@ def bound(ref, S, K, dtype, sum_slack=1):
     return S.mul_(K).mul_(sum_slack * U32).add_(ref.abs(), alpha=U_STORE[dtype]).add_(U32)
 
 
-# ---- strip heights (csrc/conv_s2d.hip s2d_strip_rows, conv_s2u.hip s2u_strip_rows, conv_d1.hip d1_strip_rows, conv_d1g.hip d1g_strip_rows)
+# ---- strip heights (csrc/conv_args.h strip_rows(per_img, rows, step, want); the four rows: how s2d_ / s2u_ / d1_ / d1g_strip_rows of csrc/conv_*.hip call it)
 _STRIP_RULE = {
     # kernel: (pixels per row segment (0 = whole rows), output channels per tile (0 = one tile), first R and step, workgroups wanted)
     's2d': (128, 128, 2, 240),
