@@ -49,13 +49,11 @@ import torch
 import torch.nn.functional as F
 
 import pad_ref
-from conv_ref import U32, _hist
+from conv_ref import STRICT_REPR, U16, U32, _hist, act32, model_values  # noqa: F401  (the operand model and the strict constant live in conv_ref; re-exported)
 from deepliif_amd import _lib as L
 from deepliif_amd.geometry import ConvSpec, choose_wgrad_splitk, cpad
 
 Desc = namedtuple('Desc', 'p_role q_role step pad pad_mode p_act q_act gshape CA CB k stack_kw')
-U16 = 2.0 ** -8          # bfloat16: 8 significant bits, round to nearest
-STRICT_REPR = 3 * U16 * U16 * (1 + 2.0 ** -8)
 _MODE = {L.PAD_ZERO: 'zero', L.PAD_REFLECT: 'reflect', L.PAD_REPLICATE: 'replicate'}
 
 
@@ -80,23 +78,6 @@ def storage_dtype(policy):
 
 def prec_of(policy):
     return L.PREC_BF16X3 if policy == 'strict' else L.PREC_BF16
-
-
-def act32(act, v):
-    """the staged activation as the kernels compute it: float32"""
-    assert v.dtype == torch.float32
-    if act == L.ACT_RELU:
-        return torch.relu(v)
-    if act == L.ACT_LRELU:
-        return torch.where(v > 0, v, v * 0.2)
-    assert act == L.ACT_NONE, act
-    return v
-
-
-def model_values(v, act, policy):
-    """float64 values the kernel's documented arithmetic multiplies for the stored fp32 / bf16 tensor v"""
-    a = act32(act, v.float())
-    return a.double() if policy == 'strict' else a.bfloat16().double()
 
 
 # ---- inputs
